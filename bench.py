@@ -13,13 +13,22 @@ M-step (SciPy's SLSQP over the OU parameters of every state; the states dealt to
 Inputs (X, graph) are resident in HBM before the timed region.  Metric (BASELINE.json):
 EM-iterations/sec x nodes = N_tot * steps / wall.
 
+A plain run sets up, warms up, times the steps (no kernel timers), writes --dump-outputs if given and prints the line.
+Everything else -- per-kernel timing, roofline, the replay at the old tolerance, the whole fits, `fit_surface`, the CPU
+baseline -- runs only under --full (its --no-* options then switch single parts off).  --dump-outputs DIR writes what the
+last timed step computed as DIR/<name>.npy: the reduced E-step statistics and costs, each unit's statistics row, the
+M-step's parameters, means and covariances, and a fixed seeded sample of the labels (with its node indices).
+It sets PHMRF_DETERMINISTIC=1 unless the environment sets it: the EM carries a difference in the last bit of its
+statistics into the next iterations' parameters and labels, so only order-independent reductions make two runs with the
+same arguments write the same arrays.  Such a run times that mode (`outputs.deterministic` on the line).
+
 Multi-GPU: the syntenic blocks are independent MRFs and are DEALT to the ranks, longest first (the reference forks one
 process per block, base.py:357-362); a block that holds more than --split-above x a rank's share is cut into row tiles
 first (see the end of this text).  --scaling strong (default): the workload's units are shared out, total work fixed --
 north_star's "whole-genome run ... at 8 GPUs".  --scaling weak: N copies of the workload (an N-genome cohort) are shared
 out the same way, work per GPU fixed.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (all but cold_first_iteration_ms under --full only):
   "roofline"          the kernel with the largest device time: `frac` = algorithmic bytes (SURVEY.md 8d accounting x the
                       units the launches actually processed, COUNTED ON THE DEVICE) / the sum of the launches' OWN durations /
                       the 8 TB/s HBM peak -- own durations from HIP events with one block in flight at a time (the timed region
@@ -61,6 +70,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: kernel timers and roofline, the replay at the "
+                         "old tolerance, the whole fits, fit_surface, the CPU baseline (off: as --no-kernel-timing --no-fit "
+                         "--no-through-fit --no-old-tolerance --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float64 / float32); "
+                         "sets PHMRF_DETERMINISTIC=1 unless the environment sets it")
     ap.add_argument("--workload", default="cfg3", choices=["cfg2", "cfg3", "cfg3-chr1", "cfg4", "cfg5", "cfg5-chr1", "small"])
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="N > 1: strong = the workload's blocks dealt to the ranks (total work fixed); weak = N copies of "
@@ -116,7 +132,10 @@ def parse():
                          "carries as `at_tol_1000ppb`; energy parity with gco at 0, 1000 and 10000: tests/test_gpu_estep.py")
     ap.add_argument("--no-old-tolerance", action="store_true",
                     help="skip the second window at the stopping tolerance of rounds 3-5 (`at_tol_1000ppb`)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if not a.full:
+        a.no_kernel_timing = a.no_fit = a.no_through_fit = a.no_old_tolerance = a.no_cpu_baseline = True
+    return a
 
 
 def kernel_bytes(cls, n, K, S, D=8):
@@ -190,6 +209,10 @@ def main():
     if not 0 <= erank < eworld:
         raise SystemExit("--emulate-rank must be in [0, --emulate-world)")
 
+    if a.dump_outputs:
+        # outputs that repeat from run to run: order-independent reductions in the label solver and the statistics
+        # (include/phmrf.h; read when a block is created), unless the environment says otherwise
+        os.environ.setdefault("PHMRF_DETERMINISTIC", "1")
     from phylo_hmrf_amd import mstep, tiles, workloads
     blocks_def, S, K, nn, desc = workloads.workload(a.workload)
     my_states = [c for c in range(K) if c % eworld == erank]      # the M-step's states are dealt to the ranks
@@ -406,10 +429,12 @@ def main():
         state["covars"] = packed[K * P + K * S:].reshape(K, S, S)
 
     cost1_log = []                                             # cost1 of every EM iteration (warm-up included)
+    last_step = {}                                             # the reduced statistics of the latest EM iteration (--dump-outputs)
 
     def em_step():
         t0 = time.time()
         tot = estep_all()
+        last_step["tot"] = tot
         stats = unpack_stats(tot[:n_stats], K, S)
         cost1 = tot[n_stats + 3] / n_norm
         cost1_log.append(float(cost1))
@@ -495,6 +520,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     t_e_timed, t_m_timed = list(t_e), list(t_m)
+    dumped = None
+    if a.dump_outputs:
+        dumped = dump_outputs(a.dump_outputs, rank, world, last_step["tot"], stats_dev.cpu().numpy(), state,
+                              [(b, 0, b.n) for b in blocks] + [(tl.b, tl.own_lo, tl.own_hi) for tl in local_tiles])
     # every rank's own clocks on the line (round 6: a first run on a multi-GPU node should say WHICH rank is slow and in what):
     # mean E-step / M-step per step, the slowest E-step, nodes and units held, and the tile rounds' exchange
     per_rank = None
@@ -552,8 +581,9 @@ def main():
             agg_["propose"][2] = propose_bytes(work_, K)
         return agg_, work_
 
-    agg_dom, work = collect()                                  # the timed region: the dominant class's events, all classes' work
-    agg_dom_first, _ = collect(first=True)
+    # the timed region: the dominant class's events, all classes' work (a plain run reads neither back)
+    agg_dom, work = collect() if a.full else ({}, {})
+    agg_dom_first, _ = collect(first=True) if a.full else ({}, {})
     busy_dom = {name: union_ms(np.concatenate([b.intervals(name) for b in unit_blocks] or [np.zeros((0, 2))]))
                 for name in agg_dom} if not a.no_kernel_timing and unit_blocks else {}
     # ---- the instrumented pass: a few more EM iterations with every class timed (after the timed region, not part of `value`)
@@ -963,21 +993,21 @@ def main():
             #  iteration from one that did not)
             "ms_per_step_median": float(np.median(np.asarray(t_e_timed) + np.asarray(t_m_timed)) * 1e3),
             "cold_first_iteration_ms": cold_first_ms,
-            "fit": fit,
-            "fit_reference_start": fit_ref,
-            "fit_surface": fit_surface,
             "tile_rounds": tile_rounds,
             "per_rank": per_rank,
             **({"ab": ab} if ab else {}),
-            "at_tol_1000ppb": at_old_tol,
             "cost1": [round(c, 6) for c in cost1_log[-min(len(cost1_log), 8):]],     # the last iterations' cost1 (base.py:410)
             "build": {"source_hash": source_hash()},
             "value_estep_only": n_norm * a.steps / float(np.sum(t_e_timed)),
             "setup_s": setup_s, "block_threads": a.block_threads, "components_prepared_behind_mstep": bool(blocks and not a.no_prepare),
-            "kernels": kernels, "kernels_from": kernels_from,
-            "kernels_steps": inst_steps or a.steps, "roofline": roofline,
-            "roofline_limiter": roofline_limiter,
+            "full": a.full,
+            **({"outputs": {"dir": a.dump_outputs, "arrays": dumped,
+                             "deterministic": os.environ.get("PHMRF_DETERMINISTIC") == "1"}} if dumped else {}),
         }
+        if a.full:
+            out.update({"fit": fit, "fit_reference_start": fit_ref, "fit_surface": fit_surface, "at_tol_1000ppb": at_old_tol,
+                        "kernels": kernels, "kernels_from": kernels_from, "kernels_steps": inst_steps or a.steps,
+                        "roofline": roofline, "roofline_limiter": roofline_limiter})
         if emulating:
             out["emulated"] = {"world": eworld, "rank": erank, "nodes": n_local, "whole_blocks": len(blocks),
                                "tiles": [[g.block_id, t] for g in conductor.groups for t in sorted(g.local)],
@@ -1010,6 +1040,39 @@ KERNELS_OF_CLASS = {"strip": ["strip_cols_kernel"], "fusion": ["fusion_cols_kern
                     "propose": ["propose_grid_kernel", "propose_kernel"], "emission": ["emission_kernel"],
                     "energy": ["energy_grid_kernel", "energy_delta_grid_kernel", "energy_kernel"],
                     "posterior_stats": ["posterior_kernel"]}
+
+
+LABEL_SAMPLE = 1 << 21          # --dump-outputs: labels written per run (all of them below this), shared out over the ranks
+LABEL_SAMPLE_SEED = 20191001
+
+
+def dump_outputs(d, rank, world, tot, stats_units, state, units):
+    """--dump-outputs DIR: what the last timed EM iteration computed, as DIR/<name>.npy -- the reduced E-step statistics with
+    its four costs (`estep_stats`: K(1+S+S^2) sufficient statistics, then the pairwise, pairwise-normalised, unary costs and
+    cost1), the M-step's OU parameters, means and covariances (rank 0: they are the same on every rank), this rank's statistics
+    row per unit, and its labels (units = [(Block, first, end)] in the rank's order) -- all of them or a fixed seeded sample,
+    with the node indices the sample took.  More than one rank: the per-rank arrays carry _rank<r>.  -> the names written"""
+    os.makedirs(d, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    arrays = {"estep_stats_per_unit" + sfx: stats_units}
+    if rank == 0:
+        arrays.update(estep_stats=tot, mstep_params=state["params"], mstep_means=state["means"], mstep_covars=state["covars"])
+    n = int(sum(hi - lo for _, lo, hi in units))
+    cap = LABEL_SAMPLE // max(world, 1)
+    idx = (np.arange(n) if n <= cap
+           else np.unique(np.random.default_rng(LABEL_SAMPLE_SEED).integers(0, n, cap)))
+    labels, s0 = [], 0
+    for b, lo, hi in units:
+        j = idx[np.searchsorted(idx, s0):np.searchsorted(idx, s0 + hi - lo)] - s0
+        if len(j):
+            labels.append(b.get_labels()[lo:hi][j])
+        s0 += hi - lo
+    arrays["labels_sample" + sfx] = (np.concatenate(labels) if labels else np.zeros(0)).astype(np.float32)
+    arrays["labels_sample_index" + sfx] = idx.astype(np.float64)
+    for name, v in arrays.items():
+        v = np.asarray(v)
+        np.save(os.path.join(d, name + ".npy"), v if v.dtype == np.float32 else v.astype(np.float64))
+    return sorted(arrays)
 
 
 def pmc_traffic(workload, kernel_names):

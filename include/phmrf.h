@@ -69,9 +69,9 @@ PHMRF_API int phmrf_block_create(int64_t n, int S, int K, phmrf_block_t* out);
  * accumulated as fixed-point integers; 8 instead of 4 bytes per node and label of scratch for the component table): two
  * solves of the same inputs return identical labels.  Default: f32 / f64 atomics, labellings that can differ in a few
  * nodes from run to run (the reference is not deterministic either: random restarts, k-means).
- * SCOPE: the label solver only (phmrf_mrf_solve and the move passes).  The posterior statistics (f64 atomics across
- * workgroups) and the k-means moments of the initialisation (f32 LDS / f64 global atomics) stay order-dependent in their
- * last bits, so a seeded FIT is reproducible to rounding, not bit for bit. */
+ * SCOPE: the label solver (phmrf_mrf_solve and the move passes) and the posterior statistics and costs (phmrf_posterior_stats:
+ * one wave per workgroup, the workgroups' sums added in workgroup order).  The k-means moments of the initialisation
+ * (f32 LDS / f64 global atomics) stay order-dependent in their last bits. */
 PHMRF_API int phmrf_block_destroy(phmrf_block_t b);
 /* Run this block's kernels on a caller-owned hipStream_t (e.g. torch's current stream); NULL = the
  * block's own stream. */

@@ -534,6 +534,7 @@ int phmrf_block_destroy(phmrf_block_t b) {
   dev_free(b->comp);
   dev_free(b->comp_tab);
   dev_free(b->comp_tab64);
+  dev_free(b->post_partial);
   dev_free(b->comp_best);
   dev_free(b->comp_gain);
   dev_free(b->cc_seen);
@@ -2350,6 +2351,10 @@ static int posterior_launch(phmrf_block_t b, double beta, int estimate_type, boo
   const int ns = n_stats(b);
   PHMRF_CHECK(8 + ns <= ACCUM_DOUBLES, PHMRF_ERR_UNSUPPORTED, "K*(1+S+S*S) too large");
   if (write_post && !b->posteriors) PHMRF_TRY(dev_alloc(&b->posteriors, (size_t)b->n * b->K));
+  if (b->deterministic && !b->post_partial) {       // one row per workgroup of the kernel's grid over at most n nodes
+    const int64_t rows = std::min<int64_t>(POST_PARTIAL_ROWS, std::max<int64_t>(1, (b->n + POST_DET_TB - 1) / POST_DET_TB));
+    PHMRF_TRY(dev_alloc(&b->post_partial, (size_t)rows * (b->K * (1 + b->S + b->S * (b->S + 1) / 2) + 4)));   // 1 | x | x_s x_t
+  }
   PHMRF_TRY(zero_accum(b, 0, 4));
   PHMRF_TRY(zero_accum(b, 8, ns));
   tic(b, KC_POSTERIOR);

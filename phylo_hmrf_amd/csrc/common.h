@@ -103,6 +103,7 @@ struct phmrf_block {
   float* comp_tab = nullptr;                // device [n, K] per-root sums
   long long* comp_tab64 = nullptr;          // ... in deterministic mode: the same sums in 2^-16 fixed point (integer atomics)
   bool deterministic = false;               // PHMRF_DETERMINISTIC=1 at block creation: order-independent reductions
+  double* post_partial = nullptr;           // ... and the posterior statistics per workgroup, [<= POST_PARTIAL_ROWS][K*M + 4]
   int32_t* comp_best = nullptr;             // device [n]
   float* comp_gain = nullptr;               // device [n]
   uint8_t* cc_seen = nullptr;               // device [n]: the labels the prepared components were computed from
@@ -246,6 +247,8 @@ constexpr int UT_PAD = 64;            // floats of slack before and after the un
 constexpr int WORK_SLOTS = 9;         // see phmrf_block_get_work / _ex (slots 7, 8: what the seed masks settled)
 constexpr int WORK_BANKS = 256;       // work_acc[WORK_BANKS][WORK_SLOTS]: strips staged, their cells, staged cells (with rim), DP
                                       // steps of the strip kernels, one bank per workgroup id mod 256 (no hot address)
+constexpr int POST_PARTIAL_ROWS = 2048;  // deterministic mode: at most this many workgroups of the posterior / statistics
+constexpr int POST_DET_TB = 64;          // kernel (one partial row each), of one wave each
 constexpr int ACCUM_DOUBLES = 8192;  // >= K*(1+S+S*S)+16 for every (K,S) the posterior / statistics kernel supports
                                      // (K <= 64, S <= 8: 4,688); phmrf_posterior_stats rejects anything larger
 

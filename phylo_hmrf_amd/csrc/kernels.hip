@@ -556,6 +556,22 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // GRID: the block is the reference's 8-neighbour stencil on a grid: the neighbours are found by geometry and their
 // weights come from the forward-edge records (16 B per node, each edge stored once) instead of the explicit adjacency
 // rows (64 B per node) -- the same neighbours in the same order, so the two forms agree bit for bit.
+// Where statistic o = k * M + m of a workgroup's accumulators goes in the statistics (layout post[K] | obs[K,S] |
+// obsobsT[K,S,S]): -> its slot; *second = the mirrored slot of an off-diagonal pair (s, t), else -1
+template <int S>
+__device__ __forceinline__ int stat_slot(int K, int o, int* second) {
+  constexpr int M = 1 + S + S * (S + 1) / 2;
+  const int k = o / M, m = o - k * M;
+  *second = -1;
+  if (m == 0) return k;
+  if (m <= S) return K + k * S + (m - 1);
+  int q = m - 1 - S, ps = 0;                  // pair (s, t), s <= t, in the order the features were written; mirrored
+  while (q >= S - ps) { q -= S - ps; ++ps; }
+  const int pt = ps + q;
+  if (pt != ps) *second = K + K * S + k * S * S + pt * S + ps;
+  return K + K * S + k * S * S + ps * S + pt;
+}
+
 template <int S, int VEC, bool WRITE_POST, bool GRID>
 __global__ __launch_bounds__(256, 5) void posterior_kernel(const float* __restrict__ X, const float* __restrict__ logprob,
                                                         int64_t n, int K, int Kp, int D,
@@ -563,8 +579,11 @@ __global__ __launch_bounds__(256, 5) void posterior_kernel(const float* __restri
                                                         const uint8_t* __restrict__ labels, float beta, int use_w,
                                                         float* __restrict__ post_out, double* __restrict__ accum,
                                                         int gH, int gW, int gdiag, const float4* __restrict__ fwd_w,
-                                                        int64_t n_first) {
+                                                        int64_t n_first, double* __restrict__ partial) {
   // (nodes [n_first, n): a row tile counts the nodes it owns; their neighbours may lie outside the range)
+  // (partial != nullptr, deterministic mode: one wave per workgroup, so its LDS sums are added in program order, and the
+  //  workgroup writes them to its own row of `partial` -- KM statistics, then the four costs -- which
+  //  posterior_reduce_kernel adds in workgroup order: statistics independent of the order in which workgroups finish)
   extern __shared__ float lds[];
   constexpr int M = 1 + S + S * (S + 1) / 2;      // features [1 | x | x_s x_t, s <= t]: x x^T is symmetric
   // ... and every one of them is a product of two entries of xa = [1 | x]: only xa goes to LDS (S + 1 floats per node
@@ -767,28 +786,50 @@ __global__ __launch_bounds__(256, 5) void posterior_kernel(const float* __restri
   }
   // flush: statistics (layout post[K] | obs[K,S] | obsobsT[K,S,S]) and the three cost numerators
   __syncthreads();
-  for (int o = threadIdx.x; o < KM; o += TB) {
-    const int k = o / M, m = o - k * M;
-    if (m == 0) {
-      atomicAdd(accum + ACC_STATS + k, sacc[o]);
-    } else if (m <= S) {
-      atomicAdd(accum + ACC_STATS + K + k * S + (m - 1), sacc[o]);
-    } else {                                  // pair (s, t), s <= t, in the order the features were written; mirrored
-      int q = m - 1 - S, ps = 0;
-      while (q >= S - ps) { q -= S - ps; ++ps; }
-      const int pt = ps + q;
-      atomicAdd(accum + ACC_STATS + K + K * S + k * S * S + ps * S + pt, sacc[o]);
-      if (pt != ps) atomicAdd(accum + ACC_STATS + K + K * S + k * S * S + pt * S + ps, sacc[o]);
-    }
-  }
   const double t0 = block_sum(c_pair, red);
   const double t1 = block_sum(c_pcn, red);
   const double t2 = block_sum(c_un, red);
+  if (partial) {
+    double* row = partial + (size_t)blockIdx.x * (KM + 4);
+    for (int o = threadIdx.x; o < KM; o += TB) row[o] = sacc[o];
+    if (threadIdx.x == 0) {
+      row[KM + 0] = t0;
+      row[KM + 1] = t1;
+      row[KM + 2] = t2;
+      row[KM + 3] = t1 + t2;
+    }
+    return;
+  }
+  for (int o = threadIdx.x; o < KM; o += TB) {
+    int second;
+    const int first = stat_slot<S>(K, o, &second);
+    atomicAdd(accum + ACC_STATS + first, sacc[o]);
+    if (second >= 0) atomicAdd(accum + ACC_STATS + second, sacc[o]);
+  }
   if (threadIdx.x == 0) {
     atomicAdd(accum + ACC_COST + 0, t0);
     atomicAdd(accum + ACC_COST + 1, t1);
     atomicAdd(accum + ACC_COST + 2, t2);
     atomicAdd(accum + ACC_COST + 3, t1 + t2);
+  }
+}
+
+// Deterministic mode: the rows of posterior_kernel's workgroups added in workgroup order, one thread per statistic or cost
+template <int S>
+__global__ void posterior_reduce_kernel(const double* __restrict__ partial, int rows, int K, double* __restrict__ accum) {
+  constexpr int M = 1 + S + S * (S + 1) / 2;
+  const int KM = K * M;
+  const int o = blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= KM + 4) return;
+  double v = 0.0;
+  for (int g = 0; g < rows; ++g) v += partial[(size_t)g * (KM + 4) + o];
+  if (o >= KM) {
+    accum[ACC_COST + (o - KM)] += v;
+  } else {
+    int second;
+    const int first = stat_slot<S>(K, o, &second);
+    accum[ACC_STATS + first] += v;
+    if (second >= 0) accum[ACC_STATS + second] += v;
   }
 }
 
@@ -798,7 +839,8 @@ int launch_posterior_s(const phmrf_block* b, float beta, int estimate_type, bool
   constexpr int Mp = ((S + 1) % 2 == 0) ? S + 2 : S + 1;      // LDS holds [1 | x] per node
   const int K = b->K, Kp = padded_k(K);
   static const int tb_env = PHMRF_DEV_ENV("PHMRF_POST_TB") ? atoi(PHMRF_DEV_ENV("PHMRF_POST_TB")) : 0;     // development: tile rows
-  int TB = (tb_env == 64 || tb_env == 128 || tb_env == 256) ? tb_env : 256;
+  double* partial = b->deterministic ? b->post_partial : nullptr;
+  int TB = partial ? POST_DET_TB : (tb_env == 64 || tb_env == 128 || tb_env == 256) ? tb_env : 256;
   const size_t acc_bytes = (size_t)K * M * sizeof(double);            // the workgroup's f64 statistics
   // (the tile prefers 64 KB, which leaves two workgroups per CU; K and S at their limits -- K = 64, S = 8: 72 KB at 64 rows --
   //  take a larger share of the CU's 160 KB instead of being refused)
@@ -811,7 +853,8 @@ int launch_posterior_s(const phmrf_block* b, float beta, int estimate_type, bool
   // (round 3, packed features: 39 KB at K = 20, S = 4 = four resident workgroups per CU: 768 -> 790 us, 1024 -> 680, 1280 -> 810;
   //  then only [1 | x] in LDS: 29 KB, and 84 registers under __launch_bounds__(256, 5) = five per CU: 1024 -> 700, 1280 -> 650)
   const int64_t n_first = b->own1 >= 0 ? b->own0 : 0, n_last = b->own1 >= 0 ? b->own1 : b->n;
-  const int grid = grid_for(n_last - n_first, TB, cap_env > 0 ? cap_env : (lds <= 32 * 1024 ? 256 * 5 : (lds <= 40 * 1024 ? 256 * 4 : (lds <= 53 * 1024 ? 256 * 3 : 256 * 8))) * (256 / TB));
+  const int grid = partial ? grid_for(n_last - n_first, TB, POST_PARTIAL_ROWS)
+                           : grid_for(n_last - n_first, TB, cap_env > 0 ? cap_env : (lds <= 32 * 1024 ? 256 * 5 : (lds <= 40 * 1024 ? 256 * 4 : (lds <= 53 * 1024 ? 256 * 3 : 256 * 8))) * (256 / TB));
   const int use_w = estimate_type == 3 ? 1 : 0;
   // the grid form needs the 8-neighbour stencil's forward-edge records (phmrf_block_set_grid / build_grid_graph)
   const bool grid_form = b->has_grid && b->grid_complete && b->fwd_w && b->D == 8 && b->num_neighbor == 8;
@@ -822,7 +865,7 @@ int launch_posterior_s(const phmrf_block* b, float beta, int estimate_type, bool
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                         \
     hipLaunchKernelGGL((posterior_kernel<S, VEC_, WP_, G_>), dim3(grid), dim3(TB), lds, b->stream, b->X, b->logprob, \
                        n_last, K, Kp, b->D, b->nbr, b->wgt, b->labels, beta, use_w, b->posteriors, b->accum, b->H, b->W, \
-                       b->diagonal, b->fwd_w, n_first);                                                             \
+                       b->diagonal, b->fwd_w, n_first, partial);                                                    \
   }
 #define PHMRF_LAUNCH_POST(VEC_, WP_)                                                                                \
   if (grid_form) PHMRF_LAUNCH_POST_G(VEC_, WP_, true) else PHMRF_LAUNCH_POST_G(VEC_, WP_, false)
@@ -835,6 +878,11 @@ int launch_posterior_s(const phmrf_block* b, float beta, int estimate_type, bool
 #undef PHMRF_LAUNCH_POST
 #undef PHMRF_LAUNCH_POST_G
   PHMRF_HIP(hipGetLastError());
+  if (partial) {
+    hipLaunchKernelGGL((posterior_reduce_kernel<S>), dim3((K * M + 4 + 255) / 256), dim3(256), 0, b->stream, partial, grid, K,
+                       b->accum);
+    PHMRF_HIP(hipGetLastError());
+  }
   return PHMRF_OK;
 }
 

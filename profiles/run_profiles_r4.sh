@@ -20,20 +20,20 @@ mkdir -p $O
 bash profiles/run_pmc_by_kernel.sh $REV > $O/r4_pmc.out 2>&1
 [ -s $O/pmc_by_kernel.json ] && cp $O/pmc_by_kernel.json profiles/pmc_by_kernel.json
 echo "pmc done"
-python3 bench.py > $O/r4_bench.json 2> $O/r4_bench.err
-for t in "" _b _c; do python3 bench.py --steps 20 --warmup 5 > $O/r4_bench_steps20_warmup5$t.json 2>> $O/r4_bench.err; done
+python3 bench.py --full > $O/r4_bench.json 2> $O/r4_bench.err
+for t in "" _b _c; do python3 bench.py --full --steps 20 --warmup 5 > $O/r4_bench_steps20_warmup5$t.json 2>> $O/r4_bench.err; done
 echo "bench done"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r4_stats -- python3 bench.py --no-cpu-baseline --no-fit > $O/r4_bench_under_rocprof.json 2> $O/r4_rocprof.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r4_stats -- python3 bench.py --full --no-cpu-baseline --no-fit > $O/r4_bench_under_rocprof.json 2> $O/r4_rocprof.err
 find $O/r4_stats -name "*kernel_stats.csv" -exec cp {} $O/r4_kernel_stats.csv \;
 rm -rf $O/r4_stats
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r4_stats -- python3 bench.py --no-cpu-baseline --no-fit --block-threads 1 --mstep-workers 1 > $O/r4_bench_under_rocprof_serial.json 2>> $O/r4_rocprof.err
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r4_stats -- python3 bench.py --full --no-cpu-baseline --no-fit --block-threads 1 --mstep-workers 1 > $O/r4_bench_under_rocprof_serial.json 2>> $O/r4_rocprof.err
 find $O/r4_stats -name "*kernel_stats.csv" -exec cp {} $O/r4_kernel_stats_serial.csv \;
 rm -rf $O/r4_stats
 echo "rocprof done"
 bash tools/job_emulate_only.sh r4 8 > $O/r4_emu8.log 2>&1
 echo "emulate done"
-for w in cfg3-chr1 cfg2 cfg4; do python3 bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline > $O/r4_$w.json 2>> $O/r4_rest.err; done
-python3 bench.py --workload cfg5-chr1 --steps 3 --warmup 2 --no-cpu-baseline --no-fit > $O/r4_cfg5-chr1.json 2>> $O/r4_rest.err
+for w in cfg3-chr1 cfg2 cfg4; do python3 bench.py --full --workload $w --steps 20 --warmup 5 --no-cpu-baseline > $O/r4_$w.json 2>> $O/r4_rest.err; done
+python3 bench.py --full --workload cfg5-chr1 --steps 3 --warmup 2 --no-cpu-baseline --no-fit > $O/r4_cfg5-chr1.json 2>> $O/r4_rest.err
 echo "rest done"
 bash profiles/warm_solve_profile.sh r4 > $O/r4_warm.out 2>&1
 python3 - <<'PY'

@@ -32,12 +32,12 @@ if [ "$PART" = "a" ]; then
   bash profiles/run_pmc_by_kernel.sh $REV > $O/r5_pmc.out 2>&1
   [ -s $O/pmc_by_kernel.json ] && cp $O/pmc_by_kernel.json profiles/pmc_by_kernel.json
   echo "pmc done"
-  python3 bench.py > $O/r5_bench.json 2> $O/r5_bench.err
-  for t in "" _b _c; do python3 bench.py --steps 20 --warmup 5 > $O/r5_bench_steps20_warmup5$t.json 2>> $O/r5_bench.err; done
+  python3 bench.py --full > $O/r5_bench.json 2> $O/r5_bench.err
+  for t in "" _b _c; do python3 bench.py --full --steps 20 --warmup 5 > $O/r5_bench_steps20_warmup5$t.json 2>> $O/r5_bench.err; done
   summ r5_bench r5_bench_steps20_warmup5 r5_bench_steps20_warmup5_b r5_bench_steps20_warmup5_c
 fi
 if [ "$PART" = "b" ]; then
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r5_stats -- python3 bench.py --no-cpu-baseline --no-fit > $O/r5_bench_under_rocprof.json 2> $O/r5_rocprof.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r5_stats -- python3 bench.py --full --no-cpu-baseline --no-fit > $O/r5_bench_under_rocprof.json 2> $O/r5_rocprof.err
   find $O/r5_stats -name "*kernel_stats.csv" -exec cp {} $O/r5_kernel_stats.csv \;
   rm -rf $O/r5_stats
   bash profiles/run_profiles_r5_serial.sh
@@ -53,8 +53,8 @@ fi
 if [ "$PART" = "c" ]; then
   bash tools/job_emulate_only.sh r5 8 > $O/r5_emu8.log 2>&1
   cat $O/r5_emu8.log
-  for w in cfg3-chr1 cfg2 cfg4; do python3 bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline > $O/r5_$w.json 2>> $O/r5_rest.err; done
-  python3 bench.py --workload cfg5-chr1 --steps 3 --warmup 2 --no-cpu-baseline --no-fit > $O/r5_cfg5-chr1.json 2>> $O/r5_rest.err
+  for w in cfg3-chr1 cfg2 cfg4; do python3 bench.py --full --workload $w --steps 20 --warmup 5 --no-cpu-baseline > $O/r5_$w.json 2>> $O/r5_rest.err; done
+  python3 bench.py --full --workload cfg5-chr1 --steps 3 --warmup 2 --no-cpu-baseline --no-fit > $O/r5_cfg5-chr1.json 2>> $O/r5_rest.err
   summ r5_cfg3-chr1 r5_cfg2 r5_cfg4 r5_cfg5-chr1
   bash tools/job_tile_exchange.sh
 fi

@@ -6,7 +6,7 @@
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 O=gpurun_out; mkdir -p $O
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r5_stats -- python3 bench.py --no-cpu-baseline --no-fit --block-threads 1 --mstep-workers 1 --steps 8 --warmup 2 > $O/r5_bench_under_rocprof_serial.json 2> $O/r5_rocprof_serial.err
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r5_stats -- python3 bench.py --full --no-cpu-baseline --no-fit --block-threads 1 --mstep-workers 1 --steps 8 --warmup 2 > $O/r5_bench_under_rocprof_serial.json 2> $O/r5_rocprof_serial.err
 find $O/r5_stats -name "*kernel_stats.csv" -exec cp {} $O/r5_kernel_stats_serial.csv \;
 rm -rf $O/r5_stats
 python3 - <<'PY'

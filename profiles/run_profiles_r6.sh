@@ -32,12 +32,12 @@ if [ "$PART" = "a" ]; then
   bash profiles/run_pmc_by_kernel.sh $REV > $O/r6_pmc.out 2>&1
   [ -s $O/pmc_by_kernel.json ] && cp $O/pmc_by_kernel.json profiles/pmc_by_kernel.json
   echo "pmc done"
-  python3 bench.py > $O/r6_bench.json 2> $O/r6_bench.err
-  for t in "" _b _c; do python3 bench.py --steps 20 --warmup 5 > $O/r6_bench_steps20_warmup5$t.json 2>> $O/r6_bench.err; done
+  python3 bench.py --full > $O/r6_bench.json 2> $O/r6_bench.err
+  for t in "" _b _c; do python3 bench.py --full --steps 20 --warmup 5 > $O/r6_bench_steps20_warmup5$t.json 2>> $O/r6_bench.err; done
   summ r6_bench r6_bench_steps20_warmup5 r6_bench_steps20_warmup5_b r6_bench_steps20_warmup5_c
 fi
 if [ "$PART" = "b" ]; then
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r6_stats -- python3 bench.py --no-cpu-baseline --no-fit --no-through-fit --no-old-tolerance > $O/r6_bench_under_rocprof.json 2> $O/r6_rocprof.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r6_stats -- python3 bench.py --full --no-cpu-baseline --no-fit --no-through-fit --no-old-tolerance > $O/r6_bench_under_rocprof.json 2> $O/r6_rocprof.err
   find $O/r6_stats -name "*kernel_stats.csv" -exec cp {} $O/r6_kernel_stats.csv \;
   rm -rf $O/r6_stats
   bash profiles/run_profiles_r6_serial.sh
@@ -53,8 +53,8 @@ fi
 if [ "$PART" = "c" ]; then
   bash tools/job_emulate_only.sh r6 8 > $O/r6_emu8.log 2>&1
   cat $O/r6_emu8.log
-  for w in cfg3-chr1 cfg2 cfg4; do python3 bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline > $O/r6_$w.json 2>> $O/r6_rest.err; done
-  python3 bench.py --workload cfg5-chr1 --steps 3 --warmup 2 --no-cpu-baseline --no-fit --no-through-fit > $O/r6_cfg5-chr1.json 2>> $O/r6_rest.err
+  for w in cfg3-chr1 cfg2 cfg4; do python3 bench.py --full --workload $w --steps 20 --warmup 5 --no-cpu-baseline > $O/r6_$w.json 2>> $O/r6_rest.err; done
+  python3 bench.py --full --workload cfg5-chr1 --steps 3 --warmup 2 --no-cpu-baseline --no-fit --no-through-fit > $O/r6_cfg5-chr1.json 2>> $O/r6_rest.err
   summ r6_cfg3-chr1 r6_cfg2 r6_cfg4 r6_cfg5-chr1
   bash tools/job_tile_exchange.sh r6
 fi

@@ -10,11 +10,12 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(extra, env=None):
+def _run(extra, env=None, full=True):
     e = dict(os.environ)
     e.update(env or {})
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "small", "--steps", "2", "--warmup", "1",
-                          "--cpu-sample", "40"] + extra, cwd=ROOT, capture_output=True, text=True, timeout=900, env=e)
+                          "--cpu-sample", "40"] + (["--full"] if full else []) + extra, cwd=ROOT, capture_output=True, text=True,
+                         timeout=900, env=e)
     assert out.returncode == 0, out.stderr[-2000:]
     return json.loads(out.stdout.strip().splitlines()[-1])
 
@@ -81,6 +82,43 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     for key in ("value", "unit", "cores", "kind", "sample", "vectorised", "all_cores_upper_bound"):
         assert key in c, key
     assert c["kind"] in ("reference", "port") and c["value"] > 0 and c["vectorised"]["value"] >= c["value"] * 0.5
+
+
+def test_plain_bench_line_is_lean_and_dumps_the_last_steps_outputs(tmp_path):
+    """Without --full: the headline figures only (no kernel timers, fits, replays or CPU baseline on the line), --steps timed
+    steps, and --dump-outputs writes the last timed step's statistics, M-step result and a label sample -- the same labels
+    and statistics the line's cost1 comes from -- and writes the same arrays when run again with the same arguments."""
+    import numpy as np
+    d = _run(["--steps", "3", "--dump-outputs", str(tmp_path)], full=False)
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["full"] is False and d["value"] > 0 and d["ms_per_step"] > 0 and len(d["estep_ms_by_step"]) == 3
+    for key in ("roofline", "roofline_limiter", "kernels", "fit", "fit_reference_start", "fit_surface", "at_tol_1000ppb",
+                "cpu_baseline"):
+        assert key not in d, key
+    names = d["outputs"]["arrays"]
+    assert d["outputs"]["deterministic"] is True
+    assert set(names) == {"estep_stats", "estep_stats_per_unit", "mstep_params", "mstep_means", "mstep_covars", "labels_sample",
+                          "labels_sample_index"}
+    arr = {n: np.load(str(tmp_path / (n + ".npy"))) for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in arr.values())
+    assert sum(v.nbytes for v in arr.values()) <= 64 << 20
+    K, S = d["config"]["K"], d["config"]["S"]
+    n = sum(d["config"]["nodes_per_rank"])
+    n_stats = K * (1 + S + S * S)
+    st = arr["estep_stats"]
+    assert st.shape == (n_stats + 4,) and abs(st[n_stats + 3] / n - d["cost1"][-1]) <= 1e-6 * (1 + abs(d["cost1"][-1]))
+    assert np.allclose(arr["estep_stats_per_unit"].sum(axis=0), st)
+    assert arr["mstep_means"].shape == (K, S) and arr["mstep_covars"].shape == (K, S, S) and np.all(np.isfinite(arr["mstep_params"]))
+    lab, idx = arr["labels_sample"], arr["labels_sample_index"]
+    assert lab.shape == idx.shape and len(lab) == n and np.array_equal(idx, np.arange(n))     # small workload: every label
+    assert lab.min() >= 0 and lab.max() < K and np.array_equal(lab, np.round(lab))
+    # the same arguments again: the same inputs and the same outputs, array for array
+    again = tmp_path / "again"
+    d2 = _run(["--steps", "3", "--dump-outputs", str(again)], full=False)
+    assert d2["outputs"]["arrays"] == names
+    for name in names:
+        assert np.array_equal(np.load(str(again / (name + ".npy"))), arr[name]), name
 
 
 def test_bench_rccl_path_single_rank():

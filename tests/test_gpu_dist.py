@@ -212,10 +212,10 @@ def test_bench_two_ranks_on_one_gpu_shards_the_blocks(tmp_path):
                    OMP_NUM_THREADS="2", PHMRF_DETERMINISTIC="1")
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr",
                "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--workload",
-               "small", "--steps", "2", "--warmup", "2", "--no-cpu-baseline", "--split-above", "0.4"]
+               "small", "--steps", "2", "--warmup", "2", "--full", "--no-cpu-baseline", "--split-above", "0.4"]
         if world == 1:
             cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "small", "--steps", "2",
-                   "--warmup", "2", "--no-cpu-baseline"]
+                   "--warmup", "2", "--full", "--no-cpu-baseline"]
         out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
         assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
         return json.loads([ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")][-1])
@@ -248,7 +248,7 @@ def test_bench_four_ranks_on_one_gpu_two_split_blocks_on_disjoint_rank_pairs(tmp
     env = dict(os.environ, PHMRF_ONE_GPU="1", PHMRF_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
            "--master-port", "29757", os.path.join(ROOT, "bench.py"), "--gpus", "4", "--workload", "small", "--steps", "2",
-           "--warmup", "2", "--no-cpu-baseline"]
+           "--warmup", "2", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     d = json.loads([ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")][-1])

@@ -876,21 +876,32 @@ P2 = np.clip(P * (1 + 0.15 * rng.standard_normal(P.shape)), 1e-3, 50); mu2, cv2 
 dev = torch.device("cuda", 0)
 X = synthetic.device_observations(torch, dev, 2, N, N, True, K, mu, cv); torch.cuda.synchronize()
 n = N * (N + 1) // 2
+def stats_vec(b):
+    st, costs, _ = b.posterior_stats(1.0, 3)
+    return np.concatenate([np.ravel(v) for v in st.values()] + [costs])
 out = []
 for rep in range(3):
     b = Block(n, S, K); b.set_observations_dev(X.data_ptr()); b.sync(); b.build_grid_graph(N, N, True, 8, 0.5)
     b.emission(mu2, cv2)
     res = b.solve(1.0, energy_tol_ppb=1000, init_mode=1)           # a cold start: component moves, coarse moves, every kernel
     lab = b.get_labels()
-    out.append((hashlib.sha1(lab.tobytes()).hexdigest(), res["rounds"], repr(res["energy"])))
+    sv = stats_vec(b)
+    assert np.array_equal(sv, stats_vec(b))
+    out.append((hashlib.sha1(lab.tobytes()).hexdigest(), res["rounds"], repr(res["energy"]), hashlib.sha1(sv.tobytes()).hexdigest()))
     b.close()
+os.environ["PHMRF_DETERMINISTIC"] = "0"                          # the default reduction (atomics) on the same labelling
+b = Block(n, S, K); b.set_observations_dev(X.data_ptr()); b.sync(); b.build_grid_graph(N, N, True, 8, 0.5)
+b.emission(mu2, cv2); b.set_labels(lab)
+err = float(np.max(np.abs(stats_vec(b) - sv) / (1.0 + np.abs(sv))))
+b.close()
 print("RESULT", out)
+print("ERR", err)
 """
 
 
 def test_deterministic_mode_gives_identical_labellings():
     """PHMRF_DETERMINISTIC=1 (include/phmrf.h): three cold-start solves of the same 245,350-node block, each on a fresh
-    block, return bit-identical labels, round counts and energies.  (Without it the f32 atomics of the component move
+    block, return bit-identical labels, round counts, energies and posterior statistics.  (Without it the f32 atomics of the component move
     table make the labellings differ in a few nodes from run to run: not asserted, it is a matter of timing.)"""
     import subprocess
     import sys
@@ -901,6 +912,9 @@ def test_deterministic_mode_gives_identical_labellings():
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("RESULT")][-1]
     runs = eval(line[len("RESULT"):])
     assert len(runs) == 3 and runs[0] == runs[1] == runs[2], runs
+    # the statistics and costs too (summed in workgroup order), equal to the default atomic sums up to rounding
+    err = float([ln for ln in out.stdout.splitlines() if ln.startswith("ERR")][-1].split()[1])
+    assert err < 1e-9, err
 
 
 def test_coarse_labels_in_batches_give_the_one_by_one_sequence():

@@ -4,8 +4,8 @@
 TAG=${1:-r6}
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
-O=gpurun_out; mkdir -p $O
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-fit --no-through-fit > $O/${TAG}_base.json 2> $O/${TAG}_base.err || exit 1
+O=$(realpath -m "${OUT_DIR:-bench_outputs}"); mkdir -p $O
+python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-fit --no-through-fit > $O/${TAG}_base.json 2> $O/${TAG}_base.err || exit 1
 python3 -c "
 import json;d=json.loads(open('$O/${TAG}_base.json').read().strip().splitlines()[-1]);r=d['roofline']
 print('base: ms/step %.2f estep %.2f mstep %.2f cold %.0f | frac %.4f full %s mop %s'%(d['ms_per_step'],d['estep_ms'],d['mstep_ms'],d['cold_first_iteration_ms'],r['frac'],r['full_sweep']['own_ms'],r['mop_up']['own_ms']))"
