@@ -48,9 +48,9 @@ typedef struct phmrf_block* phmrf_block_t;
 /* ---- library ---------------------------------------------------------------------------------- */
 /* ABI version = major * 100 + minor.  110 (round 4): PHMRF_NUM_KERNEL_CLASSES is 10 and phmrf_block_get_timing takes the
  * capacity of the caller's arrays; phmrf_block_get_work writes 8 values; the resumable solve (phmrf_mrf_solve_begin ...
- * _end) and the row-tile entry points are new.  120 (round 5): phmrf_block_get_work_first, phmrf_block_get_timing_first; phmrf_solve_opts.coarse_start.  121: phmrf_block_prepare_components.  122 (round 6): phmrf_block_get_work_ex.  123: phmrf_mrf_graph_expansion.  124: phmrf_mrf_solve_group.  A binding checks phmrf_version() == PHMRF_VERSION when it loads the library
+ * _end) and the row-tile entry points are new.  120 (round 5): phmrf_block_get_work_first, phmrf_block_get_timing_first; phmrf_solve_opts.coarse_start.  121: phmrf_block_prepare_components.  122 (round 6): phmrf_block_get_work_ex.  123: phmrf_mrf_graph_expansion.  124: phmrf_mrf_solve_group.  125: phmrf_posterior_summary.  A binding checks phmrf_version() == PHMRF_VERSION when it loads the library
  * (phylo_hmrf_amd/_lib.py does). */
-#define PHMRF_VERSION 124
+#define PHMRF_VERSION 125
 PHMRF_API int phmrf_version(void);
 PHMRF_API const char* phmrf_last_error(void);
 PHMRF_API const char* phmrf_status_string(int status);
@@ -295,6 +295,15 @@ PHMRF_API int phmrf_posterior_stats(phmrf_block_t b, double beta, int estimate_t
 /* Same, results left in device memory (float64 [K+K*S+K*S*S+4], stats then costs) for an RCCL
  * all-reduce on the caller's stream; no host synchronisation. */
 PHMRF_API int phmrf_posterior_stats_dev(phmrf_block_t b, double beta, int estimate_type, double* out_dev);
+
+/* ABI 125: a per-node summary of the same conditional posteriors, for segmenting with a fitted model -- no statistics,
+ * and n (9 or 5) bytes to the host instead of n * K doubles.  Over the OWNED rows (all n unless the block is a row tile):
+ *   conf[i]    = post[i, l_i]                 host float32 [owned]: bit for bit what phmrf_posterior_stats computes
+ *   top[i]     = argmax_k post[i, k]          host uint8 [owned]: the lowest k on ties
+ *   entropy[i] = -sum_k post log post (nats)  host float32 [owned]; entropy_or_null == NULL skips it
+ * Needs labels, logprob and a graph (PHMRF_ERR_STATE otherwise); estimate_type as in phmrf_posterior_stats. */
+PHMRF_API int phmrf_posterior_summary(phmrf_block_t b, double beta, int estimate_type, float* conf, uint8_t* top,
+                                      float* entropy_or_null);
 
 /* ---- initialisation --------------------------------------------------------- */
 /* One Lloyd step of k-means on the block's device-resident observations.  The reference initialises the states

@@ -85,6 +85,10 @@ def parse_args(argv=None):
                       "--checkpoint_every-th EM iteration (parameters, cost bookkeeping, labellings, random generator)")
     parser.add_option("--checkpoint_every", default="1", help="EM iterations between checkpoints")
     parser.add_option("--resume", default="", help="continue a fit from this checkpoint (same data, states and options)")
+    parser.add_option("--save_model", default="", help="after the fit, write the model (tree, OU parameters, Gaussians, beta, "
+                      "solver and preprocessing settings) to this .npz, for --segment")
+    parser.add_option("--segment", default="", help="skip the fit: segment the data with the model saved at this path (cold "
+                      "solve from argmax, per-bin confidence) and write segment_<run_id>_<K>.mat")
     parser.add_option("-h", "--help", action="help")
     opts, _ = parser.parse_args(argv)
     return opts
@@ -177,11 +181,41 @@ def synthetic_cache(N, S, K, num_neighbor, seed):
     return X, len_vec, [edges], synthetic.tree_for(S)
 
 
+PARSER_DEFAULTS = dict(num_states="10", resolution="50000", num_neighbor="8", filter_mode="0", filter_sigma="0.25", dtype="0")
+
+
+def segment_settings(m, num_states, resolution, num_neighbor, filter_mode, filter_sigma, diagonal_type):
+    """--segment: the run's K and feature settings from the model file.  A value that differs from the parser's default is
+    an explicit one; if it also differs from the model's, the data would not be the model's features: ValueError."""
+    given = dict(num_states=num_states, resolution=resolution, num_neighbor=num_neighbor, filter_mode=filter_mode,
+                 filter_sigma=filter_sigma, dtype=diagonal_type)
+    saved = dict(num_states=m.K, resolution=m.resolution, num_neighbor=m.num_neighbor, filter_mode=m.filter_mode,
+                 filter_sigma=m.filter_sigma, dtype=m.diagonal_type)
+    out = {}
+    for k, v in given.items():
+        model_v = saved[k]
+        known = model_v is not None and np.isfinite(float(model_v)) and not (k != "filter_sigma" and int(model_v) == -1)
+        explicit = str(v) != PARSER_DEFAULTS[k]
+        if known and explicit and float(v) != float(model_v):
+            raise ValueError("--%s %s differs from the model's %s (%s): segmenting needs the features the model was fitted on"
+                             % (k, v, model_v, "--segment"))
+        out[k] = str(model_v) if known else v
+    return (out["num_states"], out["resolution"], out["num_neighbor"], out["filter_mode"], out["filter_sigma"], out["dtype"])
+
+
 def run(num_states, chromvec, root_path, multiple, species_name, sort_states, run_id1, cons_param, method_mode,
         initial_mode, initial_weight, initial_weight1, initial_magnitude, position1, position2, filter_sigma, beta,
         beta1, num_neighbor, filter_mode, conv_threshold, estimate_type, simu_version, annotation, reload_mode,
         diagonal_type, m_iter, resolution, quantile, ref_species, output_path, synthetic="0", seed="", quiet="0",
-        init_method="minibatch", warm_start="best", checkpoint="", checkpoint_every="1", resume="", energy_tol_ppb="10000"):
+        init_method="minibatch", warm_start="best", checkpoint="", checkpoint_every="1", resume="", energy_tol_ppb="10000",
+        save_model="", segment=""):
+    seg_model = None
+    if segment:
+        # the features must be made as the model's were: its settings win, an explicit different one is refused
+        from phylo_hmrf_amd.model_io import load_model
+        seg_model = load_model(segment)
+        num_states, resolution, num_neighbor, filter_mode, filter_sigma, diagonal_type = segment_settings(
+            seg_model, num_states, resolution, num_neighbor, filter_mode, filter_sigma, diagonal_type)
     run_id = int(run_id1)
     n_components1 = int(num_states)
     cons_param = float(cons_param)
@@ -207,10 +241,11 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
 
     from phylo_hmrf_amd import mstep
     from phylo_hmrf_amd.tree import load_tree_files
-    if not mstep.native_available():      # (only the Python fall-back of the M-step uses worker processes: forked before the GPU is touched)
+    if seg_model is None and not mstep.native_available():      # (only the Python fall-back of the M-step uses worker processes: forked before the GPU is touched)
         mstep._pool(min(n_components1, os.cpu_count() or 1))
 
     start = time.time()
+    x_max, species = float("nan"), None
     if synthetic > 0:
         from phylo_hmrf_amd import synthetic as _syn
         S = 4
@@ -219,6 +254,8 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
         write_cache(output_path, resolution, run_id, samples, edge_list_vec, len_vec)
     else:
         edge_list, branch_list, species = load_tree_files(data_path)       # phylo_hmrf.py:1607-1631
+        if seg_model is not None and np.asarray(edge_list).reshape(-1, 2).tolist() != seg_model.edge_list.tolist():
+            raise ValueError("the tree under --root_path is not the model's (--segment %s)" % segment)
         # (rank 0 looks, everybody follows: with --reload 1 no rank may find the cache half there while another writes it)
         have_cache = all_ranks_agree(all(os.path.exists(f) for f in cache_names(output_path, resolution, run_id)))
         if reload_mode == 1 and not have_cache:
@@ -238,7 +275,9 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
             qfile = "chrom_quantile_test.txt"                               # :1648-1664
             # (rank 0 looks, everybody follows -- as for the cache files: no rank may find the file half written by another;
             #  the file appears by rename, and x_max itself is rank 0's on every rank)
-            if quantile == 0 and all_ranks_agree(os.path.exists(qfile)):
+            if seg_model is not None and np.isfinite(seg_model.x_max):
+                x_max = float(seg_model.x_max)                              # (the model's scale, not this data's)
+            elif quantile == 0 and all_ranks_agree(os.path.exists(qfile)):
                 x_max = float(np.median(np.atleast_2d(np.loadtxt(qfile, delimiter="\t"))[:, 6])) if rank == 0 else 0.0
             else:
                 m_vec_list = preprocess.quantile_contact_vec(chrom_vec, resolution, ref_filename, filename_list, species)
@@ -256,6 +295,23 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
     print(samples.shape)
     print(np.asarray(len_vec))
 
+    if method_mode == 1 and seg_model is not None:
+        from phylo_hmrf_amd.hmrf import phyloHMRF
+        model = phyloHMRF.from_model(seg_model, samples, len_vec, edge_list_vec, random_state=seed, quiet=bool(int(quiet)))
+        print("segmenting...")
+        start = time.time()
+        res = model.segment()
+        print("segment use time: %s %s" % (time.time() - start, res["timing"]))
+        filename3 = "%s/segment_%d_%d.mat" % (output_path, run_id, n_components1)
+        if rank == 0:
+            scipy.io.savemat(filename3, {"state_vec": res["state_vec"], "len_vec": np.asarray(len_vec), "conf": res["conf"],
+                                         "top": res["top"], "energy": res["energy"]})
+        model.close()
+        if world > 1:
+            import torch.distributed as dist
+            dist.barrier()
+            dist.destroy_process_group()
+        return filename3
     if method_mode == 1:
         from phylo_hmrf_amd.hmrf import phyloHMRF
         # several GPUs: one process per GPU (init_process_group above); the blocks (and row tiles of the ones larger than a
@@ -281,6 +337,10 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
         filename3 = "%s/estimate_ou_%d_%.2f_%d.mat" % (output_path, run_id, lambda_0, n_components1)
         if rank == 0:                                   # (every rank holds the same result: state_vec is all-reduced)
             scipy.io.savemat(filename3, mdict)
+        if save_model and rank == 0:
+            pre = {} if synthetic > 0 else dict(x_max=x_max, resolution=resolution, filter_mode=int(filter_mode),
+                                                 filter_sigma=float(filter_sigma), diagonal_type=int(diagonal_type))
+            tree1.save_model(save_model, species=species, **pre)
         print(params_vecList.shape)
         tree1.close()
         mstep.close_pool()
@@ -302,4 +362,4 @@ if __name__ == "__main__":
         opts.reload, opts.dtype, opts.miter, opts.resolution, opts.quantile, opts.ref_species, opts.output,
         synthetic=opts.synthetic, seed=opts.seed, quiet=opts.quiet, init_method=opts.init, warm_start=opts.warm_start,
         checkpoint=opts.checkpoint, checkpoint_every=opts.checkpoint_every, resume=opts.resume,
-        energy_tol_ppb=opts.energy_tol_ppb)
+        energy_tol_ppb=opts.energy_tol_ppb, save_model=opts.save_model, segment=opts.segment)

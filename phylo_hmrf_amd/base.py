@@ -316,6 +316,7 @@ class _BaseGraph(object):
 
         self.params_vec1 = params_vec1.copy()                              # base.py:444
         self._ou_param_varied_constraint(params_vec)                       # base.py:445
+        self.params_vec = params_vec.copy()          # (what means_ / _covars_ now derive from: model_io.save_model)
         cost_vec = np.asarray(cost_vec)
         self._log(min_cost)
         self._log(cost_vec)

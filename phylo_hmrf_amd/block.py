@@ -18,6 +18,7 @@ class Block(object):
         h = ctypes.c_void_p()
         check(self._L.phmrf_block_create(self.n, self.S, self.K, ctypes.byref(h)))
         self._h = h
+        self.owned = (0, self.n)        # [first, last) of the nodes this block counts (set_tile: without its halo rows)
 
     # -- lifetime ---------------------------------------------------------------------------------
     def close(self):
@@ -54,11 +55,13 @@ class Block(object):
 
     def set_grid(self, H, W, diagonal, num_neighbor=8):
         check(self._L.phmrf_block_set_grid(self._h, int(H), int(W), int(bool(diagonal)), int(num_neighbor)))
+        self._geometry = (int(H), int(W), bool(diagonal))
 
     def build_grid_graph(self, H, W, diagonal, num_neighbor=8, beta1=0.5):
         """Graph built on the device from the resident observations (no host edge list)."""
         check(self._L.phmrf_block_build_grid_graph(self._h, int(H), int(W), int(bool(diagonal)), int(num_neighbor),
                                                    float(beta1)))
+        self._geometry = (int(H), int(W), bool(diagonal))
 
     def get_adjacency(self):
         D = ctypes.c_int(0)
@@ -185,6 +188,9 @@ class Block(object):
     # -- row tiles ---------------------------------------------------------------------------------
     def set_tile(self, top, bottom, sched_n=0):
         check(self._L.phmrf_block_set_tile(self._h, int(bool(top)), int(bool(bottom)), int(sched_n)))
+        H, W, diag = self._geometry
+        # the owned nodes: all but the first stored row (the upper halo) and the last (the lower one)
+        self.owned = (W if top else 0, self.n - ((W - (H - 1) if diag else W) if bottom else 0))
 
     def tile_pins(self, n_top, n_bottom):
         check(self._L.phmrf_block_tile_pins(self._h, int(n_top), int(n_bottom)))
@@ -284,6 +290,18 @@ class Block(object):
         check(self._L.phmrf_posterior_stats(self._h, float(beta), int(estimate_type), ptr_d(st), ptr_d(costs),
                                             ptr_d(post) if want_posteriors else None))
         return unpack_stats(st, K, S), costs, post
+
+    def posterior_summary(self, beta, estimate_type, want_entropy=False):
+        """per owned node (self.owned) -> (conf float32 = posterior of its label, top uint8 = the most probable state,
+        entropy float32 in nats or None)"""
+        m = self.owned[1] - self.owned[0]
+        conf, top = np.empty(m, dtype=np.float32), np.empty(m, dtype=np.uint8)
+        ent = np.empty(m, dtype=np.float32) if want_entropy else None
+        fp = ctypes.POINTER(ctypes.c_float)
+        check(self._L.phmrf_posterior_summary(self._h, float(beta), int(estimate_type), conf.ctypes.data_as(fp),
+                                              top.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                              ent.ctypes.data_as(fp) if want_entropy else None))
+        return conf, top, ent
 
     def posterior_stats_dev(self, beta, estimate_type, out_dev_ptr):
         check(self._L.phmrf_posterior_stats_dev(self._h, float(beta), int(estimate_type), ctypes.c_void_p(out_dev_ptr)))

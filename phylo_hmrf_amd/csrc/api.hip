@@ -549,6 +549,7 @@ int phmrf_block_destroy(phmrf_block_t b) {
   }
   dev_free(b->emis_params);
   dev_free(b->posteriors);
+  dev_free(b->summary);
   for (int r = 0; r < 2; ++r) {
     dev_free(b->pin_save[r]);
     dev_free(b->pin_label[r]);
@@ -2387,6 +2388,27 @@ int phmrf_posterior_stats_dev(phmrf_block_t b, double beta, int estimate_type, d
   const int ns = n_stats(b);
   PHMRF_HIP(hipMemcpyAsync(out_dev, b->accum + 8, ns * sizeof(double), hipMemcpyDeviceToDevice, b->stream));
   PHMRF_HIP(hipMemcpyAsync(out_dev + ns, b->accum, 4 * sizeof(double), hipMemcpyDeviceToDevice, b->stream));
+  return PHMRF_OK;
+}
+
+// per-node summary of the posteriors of the owned rows (no statistics): three device arrays, then one download each
+int phmrf_posterior_summary(phmrf_block_t b, double beta, int estimate_type, float* conf, uint8_t* top, float* entropy_or_null) {
+  PHMRF_CHECK(b && conf && top, PHMRF_ERR_INVALID, "NULL argument");
+  PHMRF_TRY(check_solvable(b));
+  PHMRF_CHECK(b->has_labels, PHMRF_ERR_STATE, "labels not set (phmrf_block_set_labels or a solve)");
+  const int64_t n_first = b->own1 >= 0 ? b->own0 : 0, n_last = b->own1 >= 0 ? b->own1 : b->n;
+  const int64_t m = n_last - n_first;
+  if (m <= 0) return PHMRF_OK;
+  if (!b->summary) PHMRF_TRY(dev_alloc(&b->summary, (size_t)b->n * (2 * sizeof(float) + 1)));
+  float* d_conf = reinterpret_cast<float*>(b->summary);
+  float* d_ent = d_conf + b->n;
+  uint8_t* d_top = reinterpret_cast<uint8_t*>(d_ent + b->n);
+  PHMRF_TRY(launch_posterior_summary(b, (float)beta, estimate_type, d_conf, d_top, entropy_or_null ? d_ent : nullptr));
+  PHMRF_HIP(hipMemcpyAsync(conf, d_conf, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+  PHMRF_HIP(hipMemcpyAsync(top, d_top, (size_t)m, hipMemcpyDeviceToHost, b->stream));
+  if (entropy_or_null)
+    PHMRF_HIP(hipMemcpyAsync(entropy_or_null, d_ent, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+  PHMRF_HIP(hipStreamSynchronize(b->stream));
   return PHMRF_OK;
 }
 

@@ -150,6 +150,7 @@ struct phmrf_block {
 
   float* emis_params = nullptr;             // device packed emission parameters
   float* posteriors = nullptr;              // device [n, K], allocated on demand
+  char* summary = nullptr;                  // device [n] conf f32 | [n] entropy f32 | [n] top u8 (phmrf_posterior_summary), on demand
   double* accum = nullptr;                  // device small f64 accumulator area
   double* accum_host = nullptr;             // pinned mirror
   unsigned long long* counters = nullptr;   // device [128]
@@ -270,6 +271,8 @@ bool energy_diff_available(const phmrf_block* b);
 int launch_energy_diff(const phmrf_block* b, const uint8_t* other);   // -> accum[4], [5] += E(labels) - E(other) (unary, pair)
 int launch_energy_delta(const phmrf_block* b, double* accum_at = nullptr);   // -> accum[4], [5] (or accum_at[0], [1]) += the change since labels_eval / eval_tick
 int launch_posterior_stats(const phmrf_block* b, float beta, int estimate_type, bool write_posteriors);
+int launch_posterior_summary(const phmrf_block* b, float beta, int estimate_type, float* conf, uint8_t* top,
+                             float* entropy);   // owned nodes: conf, top, entropy (NULL: skipped) at i - own0
 int launch_chain_colour(const phmrf_block* b, float beta, int family, int colour, int phase);
 int launch_component_pass(phmrf_block* b, float beta);
 int launch_component_prepare(phmrf_block* b);

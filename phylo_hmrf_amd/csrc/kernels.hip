@@ -886,7 +886,143 @@ int launch_posterior_s(const phmrf_block* b, float beta, int estimate_type, bool
   return PHMRF_OK;
 }
 
+// Per-node summary of the same conditional posterior as posterior_kernel, without statistics: conf = post[l_i] (f32),
+// top = argmax_k post (u8, lowest k on ties), optionally entropy = -sum_k post log post (f32, nats).  Outputs are indexed
+// by owned node, i - n_first.  The histogram, the tile load and the soft-max are posterior_kernel's, step for step, so
+// conf is bit for bit its posterior of the called state.  One [TB][Kp] f32 tile in LDS: a lean stream over logprob.
+template <int VEC, bool GRID>
+__global__ __launch_bounds__(256) void posterior_summary_kernel(const float* __restrict__ logprob, int64_t n, int K, int Kp, int D,
+                                                                const int32_t* __restrict__ nbr, const float* __restrict__ wgt,
+                                                                const uint8_t* __restrict__ labels, float beta, int use_w,
+                                                                int gH, int gW, int gdiag, const float4* __restrict__ fwd_w,
+                                                                int64_t n_first, float* __restrict__ conf,
+                                                                uint8_t* __restrict__ top, float* __restrict__ entropy) {
+  extern __shared__ float lds[];
+  const int TB = blockDim.x;
+  float* tile = lds;            // [TB][Kp]
+  for (int64_t base = n_first + (int64_t)blockIdx.x * TB; base < n; base += (int64_t)gridDim.x * TB) {
+    const int64_t rem = n - base;
+    const int rows = rem < TB ? (int)rem : TB;
+    const int64_t i = base + threadIdx.x;
+    const bool live = (int)threadIdx.x < rows;
+    float* row = tile + threadIdx.x * Kp;
+    int li = 0;
+    // phase 1: neighbour-label histogram h[k] in the node's own LDS row (absent neighbours skipped, isolated: onehot(l_i))
+    if (live) {
+      li = labels[i];
+      for (int k = 0; k < K; ++k) row[k] = 0.f;
+      int deg = 0;
+      if (GRID) {
+        int gi, gj;
+        grid_coords(i, gW, gdiag, &gi, &gj);
+        int64_t cc[8];
+        float ww[8];
+        grid_gather_neighbours(i, gi, gj, gH, gW, gdiag, fwd_w, cc, ww);      // (an absent neighbour is the node itself)
+        int ll[8];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) ll[t] = labels[cc[t]];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+          if (cc[t] != i) {
+            row[ll[t]] += use_w ? ww[t] : 1.f;
+            ++deg;
+          }
+        }
+      } else if (D == 8) {
+        const int32_t* nb = nbr + i * D;
+        const float* wg = wgt + i * D;
+        const int4 c0 = *reinterpret_cast<const int4*>(nb), c1 = *reinterpret_cast<const int4*>(nb + 4);
+        const float4 w0 = *reinterpret_cast<const float4*>(wg), w1 = *reinterpret_cast<const float4*>(wg + 4);
+        const int cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+        const float ww[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+        int ll[8];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) ll[t] = labels[cc[t] >= 0 ? (int64_t)cc[t] : i];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+          if (cc[t] >= 0) {
+            row[ll[t]] += use_w ? ww[t] : 1.f;
+            ++deg;
+          }
+        }
+      } else {
+        const int32_t* nb = nbr + i * D;
+        const float* wg = wgt + i * D;
+        for (int j = 0; j < D; j += 4) {
+          const int4 c = *reinterpret_cast<const int4*>(nb + j);
+          const float4 wv = *reinterpret_cast<const float4*>(wg + j);
+          const int cc[4] = {c.x, c.y, c.z, c.w};
+          const float ww[4] = {wv.x, wv.y, wv.z, wv.w};
+          int ll[4];
+#pragma unroll
+          for (int t = 0; t < 4; ++t) ll[t] = labels[cc[t] >= 0 ? (int64_t)cc[t] : i];
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            if (cc[t] >= 0) {
+              row[ll[t]] += use_w ? ww[t] : 1.f;
+              ++deg;
+            }
+          }
+        }
+      }
+      if (!deg) row[li] = 1.f;     // isolated (:421-423), as posterior_kernel
+    }
+    __syncthreads();
+    // phase 2: tile = logprob + beta*h (the soft-max below is shift-invariant: -beta*Wtot is absorbed by the max)
+    rows_to_tile<VEC, true>(logprob, nullptr, base, rows, K, Kp, tile, 1.f, beta);
+    __syncthreads();
+    // phase 3: posterior_kernel's soft-max order (max, exp, sum in k order, times the reciprocal), then the summary
+    if (live) {
+      float m = -3.0e38f;
+      for (int k = 0; k < K; ++k) m = fmaxf(m, row[k]);
+      float s1 = 0.f, ex = 0.f;
+      for (int k = 0; k < K; ++k) {
+        const float d = row[k] - m;
+        const float e = __expf(d);
+        row[k] = e;
+        s1 += e;
+        ex = fmaf(e, d, ex);
+      }
+      const float inv = 1.f / s1;
+      float best = -1.f;
+      int bk = 0;
+      for (int k = 0; k < K; ++k) {
+        const float p = row[k] * inv;
+        if (p > best) { best = p; bk = k; }
+      }
+      const int64_t o = i - n_first;
+      conf[o] = row[li] * inv;
+      top[o] = (uint8_t)bk;
+      // -sum_k p_k log p_k with log p_k = d_k - log s1: log s1 - sum_k p_k d_k (no log of a zero posterior)
+      if (entropy) entropy[o] = fmaxf(logf(s1) - ex * inv, 0.f);
+    }
+    __syncthreads();
+  }
+}
+
 }  // namespace
+
+int launch_posterior_summary(const phmrf_block* b, float beta, int estimate_type, float* conf, uint8_t* top, float* entropy) {
+  const int K = b->K, TB = tile_threads(K), Kp = padded_k(K);
+  const size_t lds = (size_t)TB * Kp * sizeof(float);
+  const int64_t n_first = b->own1 >= 0 ? b->own0 : 0, n_last = b->own1 >= 0 ? b->own1 : b->n;
+  if (n_last <= n_first) return PHMRF_OK;
+  const int grid = grid_for(n_last - n_first, TB);
+  const int use_w = estimate_type == 3 ? 1 : 0;
+  const bool grid_form = b->has_grid && b->grid_complete && b->fwd_w && b->D == 8 && b->num_neighbor == 8;
+#define PHMRF_LAUNCH_SUM(VEC_, G_)                                                                                        \
+  hipLaunchKernelGGL((posterior_summary_kernel<VEC_, G_>), dim3(grid), dim3(TB), lds, b->stream, b->logprob, n_last, K, Kp, \
+                     b->D, b->nbr, b->wgt, b->labels, beta, use_w, b->H, b->W, b->diagonal, b->fwd_w, n_first, conf, top,  \
+                     entropy)
+  switch (vec_of(K)) {
+    case 4: if (grid_form) PHMRF_LAUNCH_SUM(4, true); else PHMRF_LAUNCH_SUM(4, false); break;
+    case 2: if (grid_form) PHMRF_LAUNCH_SUM(2, true); else PHMRF_LAUNCH_SUM(2, false); break;
+    default: if (grid_form) PHMRF_LAUNCH_SUM(1, true); else PHMRF_LAUNCH_SUM(1, false); break;
+  }
+#undef PHMRF_LAUNCH_SUM
+  PHMRF_HIP(hipGetLastError());
+  return PHMRF_OK;
+}
 
 // ---- launchers --------------------------------------------------------------------------------------
 int launch_emission(const float* X, int64_t n, int S, int K, const float* packed, float* logprob, float* uT, hipStream_t st) {

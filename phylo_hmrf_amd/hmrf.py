@@ -8,6 +8,7 @@ Per syntenic block one `Block` holds X, the neighbour graph, logprob and labels 
   _compute_posteriors_graph(X, label, logprob, region_id)     :334-355
   _predict_posteriors(X, len_vec, region_id, m_queue=None)    :297-322
   _ou_param_varied_constraint(params_vec), _do_mstep(stats), _init(X), fit_accumulate_test(...)
+New: save_model(path), from_model(path, observation, ...), segment() -- a fitted model applied to other data.
 """
 from __future__ import print_function
 
@@ -108,6 +109,7 @@ class phyloHMRF(_BaseGraph):
 
         # species tree tables (phylo_hmrf.py:103-143)
         self.tree = PhyloTree(edge_list)
+        self.edge_list = [list(map(int, e)) for e in np.asarray(edge_list).reshape(-1, 2).tolist()]   # (model_io.save_model)
         self.node_num = self.tree.node_num
         self.branch_params = branch_list
         self.branch_dim = self.tree.branch_dim
@@ -429,6 +431,23 @@ class phyloHMRF(_BaseGraph):
         labels = cut_general_graph(edge_idList_undirected, edge_weightList_undirected, -logprob, self.edge_potential,
                                    n_iter=5000, algorithm="swap", init_labels=init_labels1)
         return labels, logprob
+
+    # ---- a saved model applied to new data (model_io.py, segment.py) ------------------------------
+    @classmethod
+    def from_model(cls, path, observation, len_vec, edge_list_1, **runtime):
+        """blocks and row tiles for `observation` under the model saved at `path` (no k-means, no M-step)"""
+        from .segment import from_model
+        return from_model(cls, path, observation, len_vec, edge_list_1, **runtime)
+
+    def segment(self, want_entropy=False):
+        """labels of every region from a cold solve, with per-node confidence (segment.py)"""
+        from .segment import segment
+        return segment(self, want_entropy)
+
+    def save_model(self, path, species=None, **preprocessing):
+        """the fitted model as a self-contained .npz (model_io.py)"""
+        from .model_io import save_model
+        return save_model(self, path, species=species, **preprocessing)
 
     # ---- b3 --------------------------------------------------------------------------------------
     def _compute_posteriors_graph(self, X, label, logprob, region_id):
