@@ -48,9 +48,9 @@ typedef struct phmrf_block* phmrf_block_t;
 /* ---- library ---------------------------------------------------------------------------------- */
 /* ABI version = major * 100 + minor.  110 (round 4): PHMRF_NUM_KERNEL_CLASSES is 10 and phmrf_block_get_timing takes the
  * capacity of the caller's arrays; phmrf_block_get_work writes 8 values; the resumable solve (phmrf_mrf_solve_begin ...
- * _end) and the row-tile entry points are new.  120 (round 5): phmrf_block_get_work_first, phmrf_block_get_timing_first; phmrf_solve_opts.coarse_start.  121: phmrf_block_prepare_components.  122 (round 6): phmrf_block_get_work_ex.  123: phmrf_mrf_graph_expansion.  124: phmrf_mrf_solve_group.  125: phmrf_posterior_summary.  A binding checks phmrf_version() == PHMRF_VERSION when it loads the library
+ * _end) and the row-tile entry points are new.  120 (round 5): phmrf_block_get_work_first, phmrf_block_get_timing_first; phmrf_solve_opts.coarse_start.  121: phmrf_block_prepare_components.  122 (round 6): phmrf_block_get_work_ex.  123: phmrf_mrf_graph_expansion.  124: phmrf_mrf_solve_group.  125: phmrf_posterior_summary.  126: phmrf_smooth_labels.  A binding checks phmrf_version() == PHMRF_VERSION when it loads the library
  * (phylo_hmrf_amd/_lib.py does). */
-#define PHMRF_VERSION 125
+#define PHMRF_VERSION 126
 PHMRF_API int phmrf_version(void);
 PHMRF_API const char* phmrf_last_error(void);
 PHMRF_API const char* phmrf_status_string(int status);
@@ -304,6 +304,22 @@ PHMRF_API int phmrf_posterior_stats_dev(phmrf_block_t b, double beta, int estima
  * Needs labels, logprob and a graph (PHMRF_ERR_STATE otherwise); estimate_type as in phmrf_posterior_stats. */
 PHMRF_API int phmrf_posterior_summary(phmrf_block_t b, double beta, int estimate_type, float* conf, uint8_t* top,
                                       float* entropy_or_null);
+
+/* ---- post-processing ---------------------------------------------------------------------------- */
+/* ABI 126: the reference's small-region smoothing of a state map (processing/small_region_test.m) on
+ * ONE region's labels, no block: n_iter passes over labels_dev (u8 [n], device, read only) into out_dev (u8 [n], device;
+ * may be labels_dev), both in node order -- the upper triangle row-major of an H x H diagonal block (diagonal = 1,
+ * n = H (H + 1) / 2) or the H x W matrix row-major (diagonal = 0, n = H W).  Every pass reads the map as it was at the
+ * pass's start: each 8-connected component of equal state on the full (symmetric) matrix with area <= max_area takes the
+ * most frequent other state (the lowest on ties) of the window x window neighbourhoods of its pixels (window // 2 each
+ * way, pixels whose window crosses the border do not vote) when that state holds more than half of the votes.
+ * counts_host: host int64 [3 * n_iter] or NULL: per pass, small components, components relabelled, nodes changed
+ * (components and nodes of the stored map: a diagonal block's mirror twins count once).  Queued on hip_stream (NULL: the
+ * null stream), returns when done.  Integer arithmetic throughout: the result is the same from run to run.
+ * PHMRF_ERR_INVALID for a label >= K (nothing written), window < 1, n_iter < 0, a non-square diagonal block;
+ * PHMRF_ERR_UNSUPPORTED for K > 64 or n >= 2^31 - 64. */
+PHMRF_API int phmrf_smooth_labels(const uint8_t* labels_dev, uint8_t* out_dev, int H, int W, int diagonal, int K, int window,
+                                  int64_t max_area, int n_iter, int64_t* counts_host, void* hip_stream);
 
 /* ---- initialisation --------------------------------------------------------- */
 /* One Lloyd step of k-means on the block's device-resident observations.  The reference initialises the states

@@ -89,6 +89,13 @@ def parse_args(argv=None):
                       "solver and preprocessing settings) to this .npz, for --segment")
     parser.add_option("--segment", default="", help="skip the fit: segment the data with the model saved at this path (cold "
                       "solve from argmax, per-bin confidence) and write segment_<run_id>_<K>.mat")
+    parser.add_option("--postprocess", default="", help="skip loading data and fitting: smooth the states of this "
+                      "estimate_ou_*.mat or segment_*.mat (the reference's processing/*.m), write estimate_test<chrom>.ori.txt, "
+                      ".smooth.txt and test<chrom>.region.txt in genome coordinates (--resolution) and smooth_<stem>.mat under --output")
+    parser.add_option("--smooth_window", default="5", help="--postprocess: side of the neighbourhood window")
+    parser.add_option("--smooth_area", default="-1", help="--postprocess: largest area of a small region (-1: the reference's "
+                      "80, or 25 for a region less than 100 bins high)")
+    parser.add_option("--smooth_iter", default="1", help="--postprocess: number of smoothing passes")
     parser.add_option("-h", "--help", action="help")
     opts, _ = parser.parse_args(argv)
     return opts
@@ -208,7 +215,14 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
         beta1, num_neighbor, filter_mode, conv_threshold, estimate_type, simu_version, annotation, reload_mode,
         diagonal_type, m_iter, resolution, quantile, ref_species, output_path, synthetic="0", seed="", quiet="0",
         init_method="minibatch", warm_start="best", checkpoint="", checkpoint_every="1", resume="", energy_tol_ppb="10000",
-        save_model="", segment=""):
+        save_model="", segment="", postprocess="", smooth_window="5", smooth_area="-1", smooth_iter="1"):
+    if postprocess:
+        from phylo_hmrf_amd.smooth import postprocess_file
+        area = int(smooth_area)
+        out = postprocess_file(postprocess, str(output_path), int(resolution), int(smooth_window),
+                               None if area == -1 else area, int(smooth_iter))
+        print("post-processing written: %s" % out)
+        return out
     seg_model = None
     if segment:
         # the features must be made as the model's were: its settings win, an explicit different one is refused
@@ -362,4 +376,6 @@ if __name__ == "__main__":
         opts.reload, opts.dtype, opts.miter, opts.resolution, opts.quantile, opts.ref_species, opts.output,
         synthetic=opts.synthetic, seed=opts.seed, quiet=opts.quiet, init_method=opts.init, warm_start=opts.warm_start,
         checkpoint=opts.checkpoint, checkpoint_every=opts.checkpoint_every, resume=opts.resume,
-        energy_tol_ppb=opts.energy_tol_ppb, save_model=opts.save_model, segment=opts.segment)
+        energy_tol_ppb=opts.energy_tol_ppb, save_model=opts.save_model, segment=opts.segment,
+        postprocess=opts.postprocess, smooth_window=opts.smooth_window, smooth_area=opts.smooth_area,
+        smooth_iter=opts.smooth_iter)

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PHMRF_LIB") or os.path.join(_HERE, "libphmrf.so")
 
 OK = 0
-ABI_VERSION = 125             # include/phmrf.h PHMRF_VERSION: checked against the library in load()
+ABI_VERSION = 126             # include/phmrf.h PHMRF_VERSION: checked against the library in load()
 NUM_KERNEL_CLASSES = 10
 KERNEL_CLASSES = ("emission", "icm", "chain", "component", "energy", "posterior_stats", "strip", "propose", "coarse", "fusion")
 
@@ -99,6 +99,7 @@ SIGNATURES = {
     "phmrf_posterior_stats": [_vp, _d, _i, _dp, _dp, _dp],
     "phmrf_posterior_stats_dev": [_vp, _d, _i, _vp],
     "phmrf_posterior_summary": [_vp, _d, _i, _fp, ctypes.POINTER(ctypes.c_uint8), _fp],
+    "phmrf_smooth_labels": [_vp, _vp, _i, _i, _i, _i, _i, _i64, _i, _lp, _vp],
     "phmrf_kmeans_step": [_vp, _dp, _i, _dp],
     "phmrf_kmeans_moments": [_vp, _dp, _i, _dp],
     "phmrf_block_enable_timing": [_vp, _i],

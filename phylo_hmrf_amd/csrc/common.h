@@ -276,6 +276,7 @@ int launch_posterior_summary(const phmrf_block* b, float beta, int estimate_type
 int launch_chain_colour(const phmrf_block* b, float beta, int family, int colour, int phase);
 int launch_component_pass(phmrf_block* b, float beta);
 int launch_component_prepare(phmrf_block* b);
+int launch_grid_components(int32_t* comp, int64_t n, int W, int diagonal, const uint8_t* labels, hipStream_t st);  // bare label map
 int launch_grid_graph(const phmrf_block* b, int H, int W, int diagonal, int nn, double beta1);
 int launch_propose(phmrf_block* b, float beta);  // best alternative label per node -> labels_tmp
 int launch_strip_pass(const phmrf_block* b, float beta, int orient, int shift_r, int shift_c, int alpha,

@@ -780,6 +780,17 @@ static int launch_cc(phmrf_block* b, const int* gate) {
   return PHMRF_OK;
 }
 
+// The same components of a bare label map on the complete 8-neighbour grid (smooth.hip): comp[v] = the smallest node id of
+// v's component.  No block, no move table (the flatten kernel clears no rows with K = 0).
+int launch_grid_components(int32_t* comp, int64_t n, int W, int diagonal, const uint8_t* labels, hipStream_t st) {
+  const int g = grid1d(n);
+  hipLaunchKernelGGL(cc_init_grid_kernel, dim3(g), dim3(256), 0, st, comp, n, W, diagonal, labels, nullptr);
+  hipLaunchKernelGGL(cc_union_grid_kernel, dim3(g), dim3(256), 0, st, comp, n, W, diagonal, labels, nullptr);
+  hipLaunchKernelGGL(cc_flatten_kernel, dim3(g), dim3(256), 0, st, comp, n, nullptr, 0, nullptr, nullptr);
+  PHMRF_HIP(hipGetLastError());
+  return PHMRF_OK;
+}
+
 static int ensure_component_buffers(phmrf_block* b) {
   const int64_t n = b->n;
   PHMRF_TRY(ensure(&b->comp, (size_t)n));
