@@ -128,30 +128,10 @@ void free_family(ChainFamily& f) {
 // (row, col) of node id under the block geometry
 struct Geometry {
   int H, W, diagonal;
-  std::vector<int64_t> row_start;  // diagonal: first node id of each row
-  explicit Geometry(int H_, int W_, int diag) : H(H_), W(W_), diagonal(diag) {
-    if (diagonal) {
-      row_start.resize(H + 1);
-      int64_t s = 0;
-      for (int i = 0; i < H; ++i) {
-        row_start[i] = s;
-        s += W - i;
-      }
-      row_start[H] = s;
-    }
-  }
-  int64_t count() const { return diagonal ? row_start[H] : (int64_t)H * W; }
-  void coords(int64_t id, int* i, int* j) const {
-    if (!diagonal) {
-      *i = (int)(id / W);
-      *j = (int)(id % W);
-    } else {
-      int r = (int)(std::upper_bound(row_start.begin(), row_start.end(), id) - row_start.begin()) - 1;
-      *i = r;
-      *j = r + (int)(id - row_start[r]);
-    }
-  }
-  int64_t id(int i, int j) const { return diagonal ? row_start[i] + (j - i) : (int64_t)i * W + j; }
+  explicit Geometry(int H_, int W_, int diag) : H(H_), W(W_), diagonal(diag) {}
+  int64_t count() const { return grid_row_first(H, W, diagonal); }
+  void coords(int64_t id, int* i, int* j) const { grid_coords(id, W, diagonal, i, j); }
+  int64_t id(int i, int j) const { return grid_row_base(i, W, diagonal) + j; }
   bool valid(int i, int j) const { return i >= 0 && i < H && j >= 0 && j < W && (!diagonal || i <= j); }
 };
 
@@ -1458,21 +1438,19 @@ void solve_scope_exit(phmrf_block* b) {
 }
 
 // first node of grid row i (i == H: n)
-int64_t tile_row_first(const phmrf_block* b, int i) {
-  return b->diagonal ? (int64_t)i * b->W - ((int64_t)i * (i - 1)) / 2 : (int64_t)i * b->W;
-}
+static int64_t row_first(const phmrf_block* b, int i) { return grid_row_first(i, b->W, b->diagonal); }
 
 // queue the copy of a tile's first and last owned rows into the pinned staging buffer (top row first); whoever
 // synchronises the stream next finds them there (phmrf_block_tile_get_boundary then copies without touching the device)
 int tile_queue_boundary(phmrf_block* b) {
   int64_t off = 0;
   if (b->tile_top) {
-    const int64_t tf = tile_row_first(b, 1), tc = tile_row_first(b, 2) - tf;
+    const int64_t tf = row_first(b, 1), tc = row_first(b, 2) - tf;
     PHMRF_HIP(hipMemcpyAsync(b->xfer_host, b->labels + tf, (size_t)tc, hipMemcpyDeviceToHost, b->stream));
     off = tc;
   }
   if (b->tile_bot) {
-    const int64_t bf = tile_row_first(b, b->H - 2), bc = tile_row_first(b, b->H - 1) - bf;
+    const int64_t bf = row_first(b, b->H - 2), bc = row_first(b, b->H - 1) - bf;
     PHMRF_HIP(hipMemcpyAsync(b->xfer_host + off, b->labels + bf, (size_t)bc, hipMemcpyDeviceToHost, b->stream));
   }
   b->boundary_queued = true;
@@ -2197,9 +2175,6 @@ int phmrf_mrf_solve_group(phmrf_block_t* blocks, int n_blocks, double beta, cons
 }
 
 // ---- row tiles (tile.hip) -----------------------------------------------------------------------
-static int64_t row_first(const phmrf_block* b, int i) {      // first node of grid row i (i == H: n)
-  return b->diagonal ? (int64_t)i * b->W - ((int64_t)i * (i - 1)) / 2 : (int64_t)i * b->W;
-}
 
 int phmrf_block_set_tile(phmrf_block_t b, int top, int bottom, int64_t sched_n) {
   PHMRF_CHECK(b, PHMRF_ERR_INVALID, "block is NULL");

@@ -34,19 +34,17 @@ struct CoarseGeom {
   int Hc, Wc;            // coarse grid
 };
 
+// (the checks written out here, not grid_node's: with one more level of inlined helper the coarsen kernels lose a wave of
+//  occupancy)
 __device__ __forceinline__ int fine_node(const CoarseGeom& g, int i, int j) {
   if (i < 0 || i >= g.H || j < 0 || j >= g.W) return -1;
   if (g.diagonal) {
     if (i > j) return -1;
-    return i * g.W - (i * (i - 1)) / 2 + (j - i);
+    return grid_id<int>(i, j, g.W, 1);
   }
-  return i * g.W + j;
+  return grid_id<int>(i, j, g.W, 0);
 }
-
-__device__ __forceinline__ int coarse_node(const CoarseGeom& g, int I, int J) {
-  if (g.diagonal) return I * g.Wc - (I * (I - 1)) / 2 + (J - I);
-  return I * g.Wc + J;
-}
+__device__ __forceinline__ int coarse_node(const CoarseGeom& g, int I, int J) { return grid_id<int>(I, J, g.Wc, g.diagonal); }
 
 __device__ __forceinline__ float comp4(const float4& v, int e) { return e == 0 ? v.x : (e == 1 ? v.y : (e == 2 ? v.z : v.w)); }
 

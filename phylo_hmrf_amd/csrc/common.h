@@ -304,71 +304,92 @@ int launch_tile_pins(phmrf_block* b, int region, int64_t first, int64_t count, i
                      int64_t was_first, int64_t was_count, bool save_first);
 int launch_put_labels(phmrf_block* b, int64_t first, int64_t count, const uint8_t* src_dev);
 
-// ---- grid geometry for the kernels that find a node's neighbours by arithmetic (device code) ---------------------
-// Diagonal blocks hold the upper triangle row-major: row i starts at start(i) = i W - i (i - 1) / 2 with column i.
-__device__ __forceinline__ void grid_coords(int64_t v, int W, int diagonal, int* i, int* j) {
+// ---- grid geometry: the node layout of a grid block and its neighbour walks (host and device) ----------------------
+// A full block holds its H x W nodes row-major.  A diagonal block holds the upper triangle row-major: row i starts at
+// node grid_row_first(i) = i W - i (i - 1) / 2 with column i.  The index type I is the caller's: the register-bound strip
+// and coarse kernels count nodes in 32-bit int.
+template <class I = int64_t>
+__host__ __device__ __forceinline__ I grid_row_first(int i, int W, int diagonal) {      // i == H: the number of nodes
+  return diagonal ? (I)i * W - ((I)i * (i - 1)) / 2 : (I)i * W;
+}
+// node of (i, j) = grid_row_base(i) + j
+template <class I = int64_t>
+__host__ __device__ __forceinline__ I grid_row_base(int i, int W, int diagonal) {
+  return diagonal ? (I)i * W - ((I)i * (i - 1)) / 2 - i : (I)i * W;
+}
+// node of a cell (i, j) of the block (j >= i in a diagonal block)
+template <class I = int64_t>
+__host__ __device__ __forceinline__ I grid_id(int i, int j, int W, int diagonal) {
+  return diagonal ? grid_row_first<I>(i, W, 1) + (j - i) : (I)i * W + j;
+}
+// node of (i, j); -1 outside the block or below the diagonal
+template <class I = int64_t>
+__host__ __device__ __forceinline__ I grid_node(int i, int j, int H, int W, int diagonal) {
+  if (i < 0 || i >= H || j < 0 || j >= W || (diagonal && i > j)) return -1;
+  return grid_id<I>(i, j, W, diagonal);
+}
+__host__ __device__ __forceinline__ void grid_coords(int64_t v, int W, int diagonal, int* i, int* j) {
   if (!diagonal) {
     *i = (int)(v / W);
     *j = (int)(v - (int64_t)(*i) * W);
     return;
   }
   const double bq = 2.0 * W + 1.0;
-  int r = (int)((bq - sqrt(bq * bq - 8.0 * (double)v)) * 0.5);     // the largest i with start(i) <= v, up to rounding
+  int r = (int)((bq - sqrt(bq * bq - 8.0 * (double)v)) * 0.5);     // the largest i with grid_row_first(i) <= v, up to rounding
   r = r < 0 ? 0 : (r > W - 1 ? W - 1 : r);
-  while (r > 0 && (int64_t)r * W - ((int64_t)r * (r - 1)) / 2 > v) --r;
-  while (r + 1 < W && (int64_t)(r + 1) * W - ((int64_t)(r + 1) * r) / 2 <= v) ++r;
+  while (r > 0 && grid_row_first(r, W, 1) > v) --r;
+  while (r + 1 < W && grid_row_first(r + 1, W, 1) <= v) ++r;
   *i = r;
-  *j = r + (int)(v - ((int64_t)r * W - ((int64_t)r * (r - 1)) / 2));
-}
-// node of (i, j) = grid_row_base(i) + j
-__device__ __forceinline__ int64_t grid_row_base(int i, int W, int diagonal) {
-  return diagonal ? (int64_t)i * W - ((int64_t)i * (i - 1)) / 2 - i : (int64_t)i * W;
-}
-// f(c, w) for every grid neighbour c of node v = (i, j) with the weight w of the edge, in the order of the adjacency
-// rows (ascending ids: NW N NE W E SW S SE).  The weights come from the forward-edge records (E, SW, S, SE of a node):
-// the node's own for its forward edges, its backward neighbours' for the others.
-template <class F>
-__device__ __forceinline__ void grid_for_each_neighbour(int64_t v, int i, int j, int H, int W, int diagonal,
-                                                        const float4* __restrict__ fwd_w, F&& f) {
-  const int64_t up = grid_row_base(i - 1, W, diagonal), dn = grid_row_base(i + 1, W, diagonal);
-  const int jlo_dn = diagonal ? i + 1 : 0;            // first column of the row below (the row above starts further left)
-  const float4 own = fwd_w[v];
-  if (i > 0) {
-    if (j - 1 >= 0) { const int64_t c = up + j - 1; f(c, fwd_w[c].w); }          // NW holds the edge as its SE
-    { const int64_t c = up + j; f(c, fwd_w[c].z); }                                // N: its S
-    if (j + 1 < W) { const int64_t c = up + j + 1; f(c, fwd_w[c].y); }           // NE: its SW
-  }
-  if (j - 1 >= (diagonal ? i : 0)) { const int64_t c = v - 1; f(c, fwd_w[c].x); }  // W: its E
-  if (j + 1 < W) f(v + 1, own.x);                                                   // E
-  if (i + 1 < H) {
-    if (j - 1 >= jlo_dn) f(dn + j - 1, own.y);                                      // SW
-    if (j >= jlo_dn) f(dn + j, own.z);                                              // S
-    if (j + 1 < W) f(dn + j + 1, own.w);                                            // SE
-  }
+  *j = r + (int)(v - grid_row_first(r, W, 1));
 }
 
-// The same as arrays, every load issued before any use (absent neighbours: node v itself with weight 0): ids c[8] and
-// weights w[8] in adjacency order.  For kernels whose work per neighbour is a dependent scatter -- with the callback
-// form each neighbour's loads wait for the one before.
-__device__ __forceinline__ void grid_gather_neighbours(int64_t v, int i, int j, int H, int W, int diagonal,
-                                                       const float4* __restrict__ fwd_w, int64_t (&c)[8], float (&w)[8]) {
+// Ids c[8] of the eight neighbours of node v = (i, j) in the order of the adjacency rows (ascending ids: NW N NE W E SW S
+// SE); an absent neighbour is v itself.  Returns the mask of the present ones (bit d: c[d]).
+__host__ __device__ __forceinline__ unsigned grid_neighbour_ids(int64_t v, int i, int j, int H, int W, int diagonal,
+                                                                int64_t (&c)[8]) {
   const int64_t up = grid_row_base(i - 1, W, diagonal), dn = grid_row_base(i + 1, W, diagonal);
-  const int jlo_dn = diagonal ? i + 1 : 0;
+  const int jlo_dn = diagonal ? i + 1 : 0;            // first column of the row below (the row above starts further left)
   const bool has[8] = {i > 0 && j - 1 >= 0, i > 0, i > 0 && j + 1 < W, j - 1 >= (diagonal ? i : 0), j + 1 < W,
                        i + 1 < H && j - 1 >= jlo_dn, i + 1 < H && j >= jlo_dn, i + 1 < H && j + 1 < W};
   const int64_t id[8] = {up + j - 1, up + j, up + j + 1, v - 1, v + 1, dn + j - 1, dn + j, dn + j + 1};
+  unsigned mask = 0;
 #pragma unroll
-  for (int d = 0; d < 8; ++d) c[d] = has[d] ? id[d] : v;
+  for (int d = 0; d < 8; ++d) {
+    c[d] = has[d] ? id[d] : v;
+    mask |= has[d] ? 1u << d : 0u;
+  }
+  return mask;
+}
+
+// Ids c[4] of the four forward neighbours E, SW, S, SE of node v = (i, j) -- the edges a node's forward-edge record
+// holds; an absent neighbour is v itself, and so are all four where !on.  Ids only: the caller issues the loads.
+template <class I>
+__host__ __device__ __forceinline__ void grid_forward_ids(I v, int i, int j, int H, int W, int diagonal, bool on, I (&c)[4]) {
+  const I dn = grid_row_base<I>(i + 1, W, diagonal);
+  const int jlo = diagonal ? i + 1 : 0;
+  const bool below = on && i + 1 < H;
+  c[0] = (on && j + 1 < W) ? v + 1 : v;                 // E
+  c[1] = (below && j - 1 >= jlo) ? dn + j - 1 : v;      // SW
+  c[2] = (below && j >= jlo) ? dn + j : v;              // S
+  c[3] = (below && j + 1 < W) ? dn + j + 1 : v;         // SE
+}
+
+// The neighbours with the weights of their edges, every load issued before any use (absent neighbours: node v itself
+// with weight 0): ids c[8] and weights w[8] in adjacency order.  The weights come from the forward-edge records (E, SW,
+// S, SE of a node): the node's own for its forward edges, its backward neighbours' for the others.
+__device__ __forceinline__ void grid_gather_neighbours(int64_t v, int i, int j, int H, int W, int diagonal,
+                                                       const float4* __restrict__ fwd_w, int64_t (&c)[8], float (&w)[8]) {
+  const unsigned has = grid_neighbour_ids(v, i, j, H, W, diagonal, c);
   const float4 own = fwd_w[v];
   const float4 f0 = fwd_w[c[0]], f1 = fwd_w[c[1]], f2 = fwd_w[c[2]], f3 = fwd_w[c[3]];
-  w[0] = has[0] ? f0.w : 0.f;      // NW holds the edge as its SE
-  w[1] = has[1] ? f1.z : 0.f;      // N: its S
-  w[2] = has[2] ? f2.y : 0.f;      // NE: its SW
-  w[3] = has[3] ? f3.x : 0.f;      // W: its E
-  w[4] = has[4] ? own.x : 0.f;
-  w[5] = has[5] ? own.y : 0.f;
-  w[6] = has[6] ? own.z : 0.f;
-  w[7] = has[7] ? own.w : 0.f;
+  w[0] = (has & 1u) ? f0.w : 0.f;       // NW holds the edge as its SE
+  w[1] = (has & 2u) ? f1.z : 0.f;       // N: its S
+  w[2] = (has & 4u) ? f2.y : 0.f;       // NE: its SW
+  w[3] = (has & 8u) ? f3.x : 0.f;       // W: its E
+  w[4] = (has & 16u) ? own.x : 0.f;
+  w[5] = (has & 32u) ? own.y : 0.f;
+  w[6] = (has & 64u) ? own.z : 0.f;
+  w[7] = (has & 128u) ? own.w : 0.f;
 }
 
 }  // namespace phmrf

@@ -14,32 +14,6 @@
 namespace phmrf {
 namespace {
 
-__device__ __forceinline__ void node_coords(int64_t id, int W, int diagonal, int* i, int* j) {
-  if (!diagonal) {
-    *i = (int)(id / W);
-    *j = (int)(id - (int64_t)(*i) * W);
-    return;
-  }
-  // start(i) = i*W - i(i-1)/2 ; largest i with start(i) <= id
-  const double b = 2.0 * W + 1.0;
-  int r = (int)((b - sqrt(b * b - 8.0 * (double)id)) * 0.5);
-  if (r < 0) r = 0;
-  if (r > W - 1) r = W - 1;
-  while (r > 0 && (int64_t)r * W - ((int64_t)r * (r - 1)) / 2 > id) --r;
-  while (r + 1 < W && (int64_t)(r + 1) * W - ((int64_t)(r + 1) * r) / 2 <= id) ++r;
-  *i = r;
-  *j = r + (int)(id - ((int64_t)r * W - ((int64_t)r * (r - 1)) / 2));
-}
-
-__device__ __forceinline__ int64_t node_of(int i, int j, int H, int W, int diagonal) {
-  if (i < 0 || i >= H || j < 0 || j >= W) return -1;
-  if (diagonal) {
-    if (i > j) return -1;
-    return (int64_t)i * W - ((int64_t)i * (i - 1)) / 2 + (j - i);
-  }
-  return (int64_t)i * W + j;
-}
-
 template <int S>
 __global__ void grid_graph_kernel(const float* __restrict__ X, int64_t n, int H, int W, int diagonal, int nn,
                                   double beta1, int32_t* __restrict__ nbr, float* __restrict__ wgt) {
@@ -47,7 +21,7 @@ __global__ void grid_graph_kernel(const float* __restrict__ X, int64_t n, int H,
   const int DJ[8] = {-1, 0, 1, -1, 1, -1, 0, 1};
   for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (int64_t)gridDim.x * blockDim.x) {
     int i, j;
-    node_coords(v, W, diagonal, &i, &j);
+    grid_coords(v, W, diagonal, &i, &j);
     double x[S], nx = 0.0;
 #pragma unroll
     for (int s = 0; s < S; ++s) {
@@ -59,7 +33,7 @@ __global__ void grid_graph_kernel(const float* __restrict__ X, int64_t n, int H,
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       if (nn != 8 && DI[q] != 0 && DJ[q] != 0) continue;
-      const int64_t u = node_of(i + DI[q], j + DJ[q], H, W, diagonal);
+      const int64_t u = grid_node(i + DI[q], j + DJ[q], H, W, diagonal);
       if (u < 0) continue;
       double d = 0.0, ny = 0.0;
 #pragma unroll
@@ -90,11 +64,11 @@ __global__ void fwd_weights_kernel(int64_t n, int H, int W, int diagonal, int D,
   const int FJ[4] = {1, -1, 0, 1};
   for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (int64_t)gridDim.x * blockDim.x) {
     int i, j;
-    node_coords(v, W, diagonal, &i, &j);
+    grid_coords(v, W, diagonal, &i, &j);
     float out[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const int64_t u = node_of(i + FI[q], j + FJ[q], H, W, diagonal);
+      const int64_t u = grid_node(i + FI[q], j + FJ[q], H, W, diagonal);
       if (u < 0) continue;
       for (int x = 0; x < D; ++x)
         if (nbr[v * D + x] == (int32_t)u) out[q] = wgt[v * D + x];

@@ -344,8 +344,7 @@ __global__ __launch_bounds__(256) void energy_grid_kernel(const float* __restric
     for (int u = 0; u < UR; ++u) {
       const int i = i0 + u * stride;
       on[u] = i < row1 && j < W && !(diagonal && j < i);
-      const int64_t row = diagonal ? (int64_t)i * W - ((int64_t)i * (i - 1)) / 2 - i : (int64_t)i * W;      // node = row + j
-      node[u] = on[u] ? row + j : 0;
+      node[u] = on[u] ? grid_row_base(i, W, diagonal) + j : 0;
       lab[u] = labels[node[u]];
     }
     float un[UR];
@@ -360,15 +359,9 @@ __global__ __launch_bounds__(256) void energy_grid_kernel(const float* __restric
     int ln[UR][4];
 #pragma unroll
     for (int u = 0; u < UR; ++u) {
-      const int i = i0 + u * stride;
-      const int64_t row2 = diagonal ? (int64_t)(i + 1) * W - ((int64_t)(i + 1) * i) / 2 - (i + 1) : (int64_t)(i + 1) * W;
-      const int jlo = diagonal ? i + 1 : 0;
-      const bool below = on[u] && i + 1 < H;
-      const int64_t me = node[u];
-      ln[u][0] = labels[(on[u] && j + 1 < W) ? me + 1 : me];                             // E
-      ln[u][1] = labels[(below && j - 1 >= jlo) ? row2 + j - 1 : me];                      // SW
-      ln[u][2] = labels[(below && j >= jlo) ? row2 + j : me];                              // S
-      ln[u][3] = labels[(below && j + 1 < W) ? row2 + j + 1 : me];                         // SE
+      int64_t c[4];
+      grid_forward_ids(node[u], i0 + u * stride, j, H, W, diagonal, on[u], c);
+      ln[u][0] = labels[c[0]]; ln[u][1] = labels[c[1]]; ln[u][2] = labels[c[2]]; ln[u][3] = labels[c[3]];
     }
 #pragma unroll
     for (int u = 0; u < UR; ++u) {
@@ -414,8 +407,7 @@ __global__ __launch_bounds__(256) void energy_delta_grid_kernel(const float* __r
     for (int u = 0; u < UR; ++u) {
       const int i = i0 + u * stride;
       const bool in = i < H && j < W && !(diagonal && j < i);
-      const int64_t row = diagonal ? (int64_t)i * W - ((int64_t)i * (i - 1)) / 2 - i : (int64_t)i * W;      // node = row + j
-      node[u] = in ? row + j : 0;
+      node[u] = in ? grid_row_base(i, W, diagonal) + j : 0;
       on[u] = in && (int)stamp[node[u]] > since;
       any = any || on[u];
     }
@@ -437,17 +429,10 @@ __global__ __launch_bounds__(256) void energy_delta_grid_kernel(const float* __r
     int ln[UR][4], lp[UR][4];
 #pragma unroll
     for (int u = 0; u < UR; ++u) {
-      const int i = i0 + u * stride;
-      const int64_t row2 = diagonal ? (int64_t)(i + 1) * W - ((int64_t)(i + 1) * i) / 2 - (i + 1) : (int64_t)(i + 1) * W;
-      const int jlo = diagonal ? i + 1 : 0;
-      const bool below = on[u] && i + 1 < H;
-      const int64_t me = node[u];
-      const int64_t c0 = (on[u] && j + 1 < W) ? me + 1 : me;                               // E
-      const int64_t c1 = (below && j - 1 >= jlo) ? row2 + j - 1 : me;                      // SW
-      const int64_t c2 = (below && j >= jlo) ? row2 + j : me;                              // S
-      const int64_t c3 = (below && j + 1 < W) ? row2 + j + 1 : me;                         // SE
-      ln[u][0] = labels[c0]; ln[u][1] = labels[c1]; ln[u][2] = labels[c2]; ln[u][3] = labels[c3];
-      lp[u][0] = prev[c0]; lp[u][1] = prev[c1]; lp[u][2] = prev[c2]; lp[u][3] = prev[c3];
+      int64_t c[4];
+      grid_forward_ids(node[u], i0 + u * stride, j, H, W, diagonal, on[u], c);
+      ln[u][0] = labels[c[0]]; ln[u][1] = labels[c[1]]; ln[u][2] = labels[c[2]]; ln[u][3] = labels[c[3]];
+      lp[u][0] = prev[c[0]]; lp[u][1] = prev[c[1]]; lp[u][2] = prev[c[2]]; lp[u][3] = prev[c[3]];
     }
 #pragma unroll
     for (int u = 0; u < UR; ++u) {
@@ -492,15 +477,8 @@ __global__ __launch_bounds__(256) void energy_diff_grid_kernel(const float* __re
     for (int u = 0; u < UR; ++u) {
       const int i = i0 + u * stride;
       in[u] = i < row1 && j < W && !(diagonal && j < i);
-      const int64_t row = diagonal ? (int64_t)i * W - ((int64_t)i * (i - 1)) / 2 - i : (int64_t)i * W;      // node = row + j
-      const int64_t row2 = diagonal ? (int64_t)(i + 1) * W - ((int64_t)(i + 1) * i) / 2 - (i + 1) : (int64_t)(i + 1) * W;
-      const int jlo = diagonal ? i + 1 : 0;
-      const bool below = in[u] && i + 1 < H;
-      me[u] = in[u] ? row + j : 0;
-      c[u][0] = (in[u] && j + 1 < W) ? me[u] + 1 : me[u];                       // E
-      c[u][1] = (below && j - 1 >= jlo) ? row2 + j - 1 : me[u];                 // SW
-      c[u][2] = (below && j >= jlo) ? row2 + j : me[u];                         // S
-      c[u][3] = (below && j + 1 < W) ? row2 + j + 1 : me[u];                    // SE
+      me[u] = in[u] ? grid_row_base(i, W, diagonal) + j : 0;
+      grid_forward_ids(me[u], i, j, H, W, diagonal, in[u], c[u]);
     }
     int la[UR], lb[UR], na[UR][4], nb[UR][4];
     bool on[UR];

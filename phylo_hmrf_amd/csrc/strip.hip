@@ -37,9 +37,9 @@ __device__ __forceinline__ int strip_node(const StripGeom& g, int sr, int sc) {
   const int i = g.orient ? sc : sr, j = g.orient ? sr : sc;
   if (g.diagonal) {
     if (i > j) return -1;
-    return i * g.W - (i * (i - 1)) / 2 + (j - i);
+    return grid_id<int>(i, j, g.W, 1);
   }
-  return i * g.W + j;
+  return grid_id<int>(i, j, g.W, 0);
 }
 
 __device__ __forceinline__ float comp4f(const float4& v, int e) { return e == 0 ? v.x : (e == 1 ? v.y : (e == 2 ? v.z : v.w)); }
@@ -1316,19 +1316,19 @@ __device__ PHMRF_FILTER_INLINE unsigned long long filter_phase(StripGeom g, unsi
       lc = lc < ncols ? lc : ncols - 1;
       if (ORIENT == 0) {
         int i0 = rs0 < 0 ? 0 : (rs0 > g.H - 1 ? g.H - 1 : rs0);
-        const int rb0 = (g.diagonal ? i0 * g.W - (i0 * (i0 - 1)) / 2 - i0 : i0 * g.W) + ca;
+        const int rb0 = grid_row_base<int>(i0, g.W, g.diagonal) + ca;
         plane0 += (unsigned long long)(long long)rb0 << 2;
 #pragma unroll
         for (int r = 0; r < SH; ++r) {
           int i = rs0 + r;
           i = i < 0 ? 0 : (i > g.H - 1 ? g.H - 1 : i);
-          const int rb = (g.diagonal ? i * g.W - (i * (i - 1)) / 2 - i : i * g.W) + ca;
+          const int rb = grid_row_base<int>(i, g.W, g.diagonal) + ca;
           voffr[ORIENT == 0 ? r : 0] = (unsigned int)(rb - rb0 + lc) * 4u;
         }
       } else {
         const int i = ca + lc;
-        const int rb = g.diagonal ? i * g.W - (i * (i - 1)) / 2 - i : i * g.W;
-        const int rb0 = g.diagonal ? ca * g.W - (ca * (ca - 1)) / 2 - ca : ca * g.W;
+        const int rb = grid_row_base<int>(i, g.W, g.diagonal);
+        const int rb0 = grid_row_base<int>(ca, g.W, g.diagonal);
         voffr[0] = (unsigned int)(rb - rb0) * 4u;
         plane0 += (unsigned long long)(long long)(rb0 + rs0) << 2;
       }

@@ -75,21 +75,12 @@ __global__ __launch_bounds__(256) void put_labels_kernel(uint8_t* __restrict__ l
     if (stamp) {
       int i, j;
       grid_coords(v, W, diagonal, &i, &j);
-      const int64_t up = grid_row_base(i - 1, W, diagonal), dn = grid_row_base(i + 1, W, diagonal);
-      const int jlo_dn = diagonal ? i + 1 : 0;
+      int64_t c[8];
+      const unsigned has = grid_neighbour_ids(v, i, j, H, W, diagonal, c);
       stamp[v] = (uint16_t)tick;
-      if (i > 0) {
-        if (j - 1 >= 0) stamp[up + j - 1] = (uint16_t)tick;
-        stamp[up + j] = (uint16_t)tick;
-        if (j + 1 < W) stamp[up + j + 1] = (uint16_t)tick;
-      }
-      if (j - 1 >= (diagonal ? i : 0)) stamp[v - 1] = (uint16_t)tick;
-      if (j + 1 < W) stamp[v + 1] = (uint16_t)tick;
-      if (i + 1 < H) {
-        if (j - 1 >= jlo_dn) stamp[dn + j - 1] = (uint16_t)tick;
-        if (j >= jlo_dn) stamp[dn + j] = (uint16_t)tick;
-        if (j + 1 < W) stamp[dn + j + 1] = (uint16_t)tick;
-      }
+#pragma unroll
+      for (int d = 0; d < 8; ++d)
+        if (has & (1u << d)) stamp[c[d]] = (uint16_t)tick;
     }
   }
 }
