@@ -371,12 +371,7 @@ PHMRF_API int phmrf_block_get_work(phmrf_block_t b, int64_t* out /*[8]*/);
  * launch a roofline figure has to keep apart (bench.py: roofline.full_sweep / roofline.mop_up). */
 PHMRF_API int phmrf_block_get_work_first(phmrf_block_t b, int64_t* out /*[8]*/);
 /* ABI 122 (round 6): the same ten-entry form of both (first_round_only != 0: the _first part); min(capacity, 10) entries.
- * Entries 0..7 as above.  Inside a solve strip_scan_kernel looks at a strip's stamps, memo row and SEED MASKS before the
- * expansion launch (the per-node masks propose_grid_kernel writes: bit a = an improving expansion of label a could start
- * here); a (strip, label) pair without a seed is settled there, exactly as the filter's first pass would settle it, and is
- * NOT in out[0] / out[6]:
- *   out[8] cells x labels settled by the seed masks (no unary term read)
- *   out[9] cells of the strips whose every listed label was settled that way (never staged: not in out[5])  */
+ * Entries 0..7 as above; entries 8 and 9 always read 0 (no kernel counts into them; the layout stays ten entries wide).  */
 PHMRF_API int phmrf_block_get_work_ex(phmrf_block_t b, int first_round_only, int capacity, int64_t* out /*[capacity]*/);
 /* The timed intervals of one kernel class on a time base common to all blocks of the calling thread's device
  * (phmrf_time_base_reset marks t = 0; call it before the timed region): out = [start_ms, end_ms] pairs, at most

@@ -761,20 +761,16 @@ constexpr int SLABW = (63 + 2) * SWC;        // floats
 constexpr int SLABL = ((63 + 2) * EH + 3) / 4 * 4;   // label bytes
 constexpr int CH = 18;                       // cells per table chunk: three groups of six DP steps
 constexpr int NBUF = 8;                      // flagged labels buffered before the wave turns to the DP
-// everything strip_cols_kernel keeps in LDS: 9.9 KB with one wave per workgroup (WV = 1: the full sweeps), 11 KB with WV = 4
-// waves that share one staged strip and split its labels (round 6: the launches of a solve's late rounds, strip_cols_kernel)
-template <int WV>
-struct ColsLdsT {
+// everything strip_cols_kernel keeps in LDS (one wave per workgroup): 9.9 KB
+struct ColsLds {
   alignas(16) float tabch[CH * 36];          // DP tables of one chunk (2.6 KB; 36 = TAB)
   alignas(16) float slabw[SLABW];            // the staged rectangle, never overwritten: forward weights ...
-  unsigned long long ubuf[WV * NBUF][SH];    // U of the flagged labels, one word per strip row (NBUF entries per wave)
-  int abuf[WV * NBUF];                       // ... and which labels they are
+  unsigned long long ubuf[NBUF][SH];         // U of the flagged labels, one word per strip row
+  int abuf[NBUF];                            // ... and which labels they are
   unsigned int wk[WORK_SLOTS];
-  int nbuf[WV];                              // flagged labels per wave
-  unsigned long long left[WV];               // WV > 1: the labels a wave did not get to (its buffer was full)
+  int nbuf;
   unsigned char slabl[SLABL];                // ... and label bytes of the staged rectangle
 };
-using ColsLds = ColsLdsT<1>;
 
 // ... and of fusion_cols_kernel: the same, plus the proposal byte of every staged cell
 struct FusLds {
@@ -995,7 +991,7 @@ __device__ __forceinline__ void slab_record(const float* slabw, const unsigned c
 #ifndef PHMRF_DP_INLINE
 #define PHMRF_DP_INLINE __noinline__
 #endif
-template <int ORIENT, bool FUSION, int WV = 1>
+template <int ORIENT, bool FUSION>
 __device__ PHMRF_DP_INLINE unsigned int dp_flagged(StripGeom g, unsigned int lds, int kb, int lane,
                                                    int rs0, int ca, int ncols, int ncell, int alpha, int tick_a, int64_t n, int D,
                                                    const int32_t* nbr_, const float* uT_, uint8_t* labels_, uint16_t* stamp_,
@@ -1005,7 +1001,7 @@ __device__ PHMRF_DP_INLINE unsigned int dp_flagged(StripGeom g, unsigned int lds
     const global_ptr<uint8_t> labels = as_global(labels_);
     const global_ptr<uint16_t> stamp = as_global(stamp_);
     const global_ptr<uint16_t> mslot = as_global(mslot_);       // this move's memo entry (label alpha's, or the fusion pass's)
-    ColsLdsT<WV>* L = lds_object<ColsLdsT<WV>>(lds);
+    ColsLds* L = lds_object<ColsLds>(lds);
     const float* slabw = L->slabw;
     const unsigned char* slabl = L->slabl;
     const unsigned char* slabp = FUSION ? lds_object<FusLds>(lds)->slabp : L->slabl;
@@ -1185,20 +1181,19 @@ __device__ PHMRF_DP_INLINE unsigned int dp_flagged(StripGeom g, unsigned int lds
 #ifndef PHMRF_FILTER_INLINE
 #define PHMRF_FILTER_INLINE __forceinline__
 #endif
-template <int ORIENT, int WV = 1>
+template <int ORIENT>
 __device__ PHMRF_FILTER_INLINE unsigned long long filter_phase(StripGeom g, unsigned int lds, int lane, int rs0_, int ca_, int ncols_, int ncell_,
                                                              unsigned long long v0_, unsigned long long v1_, unsigned long long v2_,
                                                              unsigned long long v3_, unsigned long long v4_, unsigned long long todo_,
-                                                             int64_t n, const float* uT_, uint16_t* mrow_, int tick0_, int peel_max_,
-                                                             int wslot = 0) {
+                                                             int64_t n, const float* uT_, uint16_t* mrow_, int tick0_, int peel_max_) {
     const global_ptr<const float> uT = as_global(uT_);
     const global_ptr<uint16_t> mrow = as_global(mrow_);
-    ColsLdsT<WV>* L = lds_object<ColsLdsT<WV>>(lds);
+    ColsLds* L = lds_object<ColsLds>(lds);
     const float* slabw = L->slabw;
     const unsigned char* slabl = L->slabl;
-    unsigned long long (*ubuf)[SH] = L->ubuf + (WV > 1 ? wslot * NBUF : 0);      // (this wave's share of the buffer)
-    int* abuf = L->abuf + (WV > 1 ? wslot * NBUF : 0);
-    int* nbuf_out = &L->nbuf[WV > 1 ? wslot : 0];
+    unsigned long long (*ubuf)[SH] = L->ubuf;
+    int* abuf = L->abuf;
+    int* nbuf_out = &L->nbuf;
     unsigned int* wk = L->wk;
 #define PHMRF_UNI64(x) (((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)((x) >> 32)) << 32) | \
                         (unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(x)))
@@ -1496,131 +1491,19 @@ __device__ __forceinline__ int strip_of_slot(const StripGeom& g, int q) {
   return q;
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// strip_scan_kernel (round 6): what every strip of the launch that follows has to do, decided BEFORE that launch by a light
-// kernel (no LDS slab, ~30 VGPRs, four strips per workgroup) instead of in the prologue of its 127-VGPR, 10 KB-LDS waves:
-//   * the memo test: the strip's newest change stamp against the ticks of its labels' last quiet runs (as before);
-//   * the SEED MASKS (expansions only): the OR over the strip's cells of the per-node masks propose_grid_kernel wrote.  A
-//     label none of whose bits is set has no seed on this strip in the filter's first pass, hence in no pass: it is quiet
-//     exactly as if the filter had run, gets its memo entry here, and the expansion kernel never loads its unary terms.  The
-//     masks are used only where no cell of the strip carries a stamp later than the proposals' launch (seed_tick): a label
-//     changed since then in or next to the strip makes every cell it touches carry one (dilated stamps).
-// out[2 slot] = the labels the memo leaves (what the strip falls back to after a move of its own: the masks are stale
-// then), out[2 slot + 1] = those that also have a seed -- 0: the launch's workgroup returns after one scalar load.
-// FUSION: the fusion pass's memo entry (slot K) alone; out[2 slot] = out[2 slot + 1] = 1 when the pass has to look.
-template <int ORIENT, bool FUSION>
-__global__ __launch_bounds__(256) void strip_scan_kernel(StripGeom g, int K, unsigned long long label_mask,
-                                                         const uint16_t* __restrict__ stamp, uint16_t* __restrict__ memo, int tick0,
-                                                         const unsigned long long* __restrict__ seed, int seed_tick,
-                                                         unsigned long long* __restrict__ out, unsigned long long* __restrict__ work) {
-  __shared__ unsigned int acc[2];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int nstrips = g.nbands * g.nsegs;
-  const int nslots = strip_slots(ORIENT, g.nbands, g.nsegs, g.xcd);
-  if (threadIdx.x < 2) acc[threadIdx.x] = 0u;
-  __syncthreads();
-  for (int base = blockIdx.x * 4; base < nslots; base += gridDim.x * 4) {
-    const int slot = __builtin_amdgcn_readfirstlane(base + wv);
-    if (slot >= nslots) continue;
-    unsigned long long tf = 0ull, td = 0ull;
-    const int strip = strip_of_slot<ORIENT>(g, slot);
-    if (strip >= 0 && strip < nstrips) {
-      const int bnd = strip / g.nsegs;
-      const int seg = strip - bnd * g.nsegs;
-      const int rs0 = bnd * (SH + 1) - g.shift_r;
-      const int cs0 = seg * 64 - g.shift_c;
-      const int ca = cs0 > 0 ? cs0 : 0;
-      const int cb = (cs0 + SL < g.Ws) ? cs0 + SL : g.Ws;
-      const int ncols = cb > ca ? cb - ca : 0;
-      const bool empty = ncols <= 0 ||
-                         (g.diagonal && (ORIENT == 0 ? (rs0 > 0 ? rs0 : 0) > cb - 1 : ca > (rs0 + SH - 1 < g.Hs - 1 ? rs0 + SH - 1 : g.Hs - 1)));
-      if (!empty) {
-        int nd[SH];
-#pragma unroll
-        for (int r = 0; r < SH; ++r) nd[r] = lane < ncols ? strip_node(g, rs0 + r, ca + lane) : -1;
-        const uint16_t* mrow = memo + (int64_t)strip * (K + 1);
-        // every load of the wave before any use
-        int st[SH];
-        unsigned long long sm[SH];
-#pragma unroll
-        for (int r = 0; r < SH; ++r) st[r] = stamp[nd[r] >= 0 ? nd[r] : 0];
-        const int lq = FUSION ? (int)mrow[K] : (lane < K ? (int)mrow[lane] : 0);
-        if (!FUSION && seed) {
-#pragma unroll
-          for (int r = 0; r < SH; ++r) sm[r] = seed[nd[r] >= 0 ? nd[r] : 0];
-        }
-        int nw = 0;
-        unsigned int have = 0u;
-#pragma unroll
-        for (int r = 0; r < SH; ++r) {
-          nw = (nd[r] >= 0 && st[r] > nw) ? st[r] : nw;
-          have |= nd[r] >= 0 ? 1u : 0u;
-        }
-        unsigned int s0 = 0u, s1 = 0u;
-        if (!FUSION && seed) {
-#pragma unroll
-          for (int r = 0; r < SH; ++r) {
-            s0 |= nd[r] >= 0 ? (unsigned int)sm[r] : 0u;
-            s1 |= nd[r] >= 0 ? (unsigned int)(sm[r] >> 32) : 0u;
-          }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-          const int o2 = __shfl_xor(nw, off, 64);
-          nw = o2 > nw ? o2 : nw;
-          if (!FUSION && seed) {
-            s0 |= (unsigned int)__shfl_xor((int)s0, off, 64);
-            s1 |= (unsigned int)__shfl_xor((int)s1, off, 64);
-          }
-        }
-        const bool any_node = __ballot(have != 0u) != 0ull;
-        if (any_node) {
-          if (FUSION) {
-            tf = td = (lq && nw < lq) ? 0ull : 1ull;
-          } else {
-            tf = label_mask & __ballot(lane < K && !(lq && nw < lq));
-            td = tf;
-            if (seed && nw <= seed_tick) {
-              td = tf & (((unsigned long long)s1 << 32) | (unsigned long long)s0);
-              const unsigned long long pruned = tf & ~td;
-              // quiet without the filter: the memo entry the filter would have written (lane <-> label)
-              if ((pruned >> lane) & 1ull) const_cast<uint16_t*>(mrow)[lane] = (uint16_t)(tick0 + lane);
-              if (lane == 0 && pruned) {
-                const unsigned int cells = (unsigned int)(ncols * SH);
-                atomicAdd(&acc[0], (unsigned int)__popcll(pruned) * cells);     // label cells settled by the masks
-                if (!td) atomicAdd(&acc[1], cells);                             // ... cells of strips settled entirely
-              }
-            }
-          }
-        }
-      }
-    }
-    if (lane == 0) {
-      out[2 * (int64_t)slot] = tf;
-      out[2 * (int64_t)slot + 1] = td;
-    }
-  }
-  __syncthreads();
-  if (work && threadIdx.x < 2) {
-    const unsigned int v = acc[threadIdx.x];
-    if (v) atomicAdd(work + (blockIdx.x & (WORK_BANKS - 1)) * WORK_SLOTS + 7 + threadIdx.x, (unsigned long long)v);
-  }
-}
-
 #ifndef PHMRF_COLS_WPE
 #define PHMRF_COLS_WPE 4
 #endif
-template <int ORIENT, int WV = 1>
-__global__ __launch_bounds__(64 * WV, PHMRF_COLS_WPE) void strip_cols_kernel(StripGeom g, int64_t n, int K, int D,
+template <int ORIENT>
+__global__ __launch_bounds__(64, PHMRF_COLS_WPE) void strip_cols_kernel(StripGeom g, int64_t n, int K, int D,
                                                                          const int32_t* __restrict__ nbr,
                                                                          const float4* __restrict__ fwd_w,
                                                                          const float* __restrict__ uT, uint8_t* __restrict__ labels,
                                                                          float beta, unsigned long long label_mask,
                                                                          unsigned long long* __restrict__ changed,
                                                                          uint16_t* __restrict__ stamp, uint16_t* __restrict__ memo,
-                                                                         int tick0, unsigned long long* __restrict__ work, int peel_max,
-                                                                         const unsigned long long* __restrict__ scan) {
-  __shared__ ColsLdsT<WV> lds_pool;
+                                                                         int tick0, unsigned long long* __restrict__ work, int peel_max) {
+  __shared__ ColsLds lds_pool;
   float* slabw = lds_pool.slabw;
   unsigned char* slabl = lds_pool.slabl;
   int* abuf = lds_pool.abuf;
@@ -1649,15 +1532,7 @@ __global__ __launch_bounds__(64 * WV, PHMRF_COLS_WPE) void strip_cols_kernel(Str
 
   const int nslots = strip_slots(ORIENT, g.nbands, g.nsegs, g.xcd);
   for (int slot_v = blockIdx.x; slot_v < nslots; slot_v += gridDim.x) {
-    const int slot_u = __builtin_amdgcn_readfirstlane(slot_v);
-    // (inside a solve strip_scan_kernel has looked at the strip's stamps, memo row and seed masks: two words per slot)
-    unsigned long long todo = label_mask, todo_full = label_mask;
-    if (scan) {
-      todo_full = scan[2 * (int64_t)slot_u];
-      todo = scan[2 * (int64_t)slot_u + 1];
-      if (!todo) continue;
-    }
-    const int strip = strip_of_slot<ORIENT>(g, slot_u);
+    const int strip = strip_of_slot<ORIENT>(g, __builtin_amdgcn_readfirstlane(slot_v));
     if (strip < 0 || strip >= nstrips) continue;
     const int bnd = strip / g.nsegs;
     const int seg = strip - bnd * g.nsegs;
@@ -1676,13 +1551,14 @@ __global__ __launch_bounds__(64 * WV, PHMRF_COLS_WPE) void strip_cols_kernel(Str
 
     // ---- column layout: lane c <-> strip column c; the node of row r is nodec[r] (-1: none)
     unsigned long long valid[SH];
+    unsigned long long todo = label_mask;
     uint16_t* mrow = memo ? memo + (int64_t)strip * (K + 1) : nullptr;
     {
       int nw = 0;
       int nd[SH];
 #pragma unroll
       for (int r = 0; r < SH; ++r) nd[r] = lane < ncols ? strip_node(g, rs0 + r, ca + lane) : -1;
-      if (mrow && !scan) {
+      if (mrow) {
 #pragma unroll
         for (int r = 0; r < SH; ++r) {
           const int st = stamp[nd[r] >= 0 ? nd[r] : 0];
@@ -1695,170 +1571,86 @@ __global__ __launch_bounds__(64 * WV, PHMRF_COLS_WPE) void strip_cols_kernel(Str
         }
         const int lq = lane < K ? (int)mrow[lane] : 0;
         todo &= __ballot(lane < K && !(lq && nw < lq));
-        todo_full = todo;
       }
 #pragma unroll
       for (int r = 0; r < SH; ++r) valid[r] = __ballot(nd[r] >= 0);
     }
     todo = ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(todo >> 32)) << 32) |
            (unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)todo);
-    todo_full = ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(todo_full >> 32)) << 32) |
-                (unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)todo_full);
     if (!todo || !(valid[0] | valid[1] | valid[2] | valid[3] | valid[4])) continue;
-    auto stage_strip = [&]() {
-      // ---- staging (as strip_kernel, step A): labels and forward weights of the strip's rectangle and rim -> LDS
-      constexpr int NEP = (ECELLS + 63) / 64;
-      int enode[NEP], eidx[NEP];
-#pragma unroll
-      for (int q = 0; q < NEP; ++q) {
-        int er, ec;
-        if (ORIENT == 0) {
-          int l2 = lane;
-          asm volatile("" : "+v"(l2));
-          er = q < EH ? q : l2;
-          ec = q < EH ? l2 : 64;
-          if (q >= EH && l2 >= EH) ec = 1 << 20;
-        } else {
-          int e = q * 64 + lane;
-          asm volatile("" : "+v"(e));
-          ec = e / EH;
-          er = e - ec * EH;
-        }
-        const bool have = ec < ncols + 2;
-        eidx[q] = have ? ec * EH + er : -1;
-        enode[q] = have ? strip_node(g, rs0 - 1 + er, ca - 1 + ec) : -1;
-      }
-      int elab[NEP];
-      float4 ef[NEP];
-#pragma unroll
-      for (int q = 0; q < NEP; ++q) {
-        const int node = enode[q];
-        elab[q] = 0;
-        ef[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (node >= 0) {
-          elab[q] = labels[node];
-          ef[q] = fwd_w[node];
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int q = 0; q < NEP; ++q) {
-        const int e = eidx[q];
-        if (e >= 0) {
-          const int ec = e / EH, er = e - ec * EH;
-          float* wr = slabw + ec * SWC + er * 4;
-          if (er < EH - 1) {
-            wr[0] = ef[q].x * beta;
-            wr[1] = ef[q].y * beta;
-            wr[2] = ef[q].z * beta;
-            wr[3] = ef[q].w * beta;
-          } else {
-            // the bottom rim row holds one edge the strip needs, and only in orientation 1: its cells' grid edge (+1, -1),
-            // which runs to strip row 4 of the next column; it lives in the column's 25th word
-            wr[0] = ef[q].y * beta;
-          }
-          slabl[e] = (unsigned char)(enode[q] >= 0 ? elab[q] : 0);
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      if (lane == 0) {
-#if !defined(PHMRF_PHASE_CLOCK) && !defined(PHMRF_FILTER_STATS)
-        atomicAdd(&wk[2], (unsigned int)(EH * (ncols + 2)));
-        atomicAdd(&wk[4], (unsigned int)ncell);
-#endif
-      }
-    };
+    const unsigned long long todo_full = todo;   // (after a move every later label of this set is filtered again)
     bool staged = false;
-    if constexpr (WV > 1) {
-      // ---- WV waves on ONE strip (the launches of a solve's late rounds, where a handful of dirty strips is all there is and
-      //      a launch takes as long as one wave needs to walk one strip's labels in sequence).  Wave 0 stages the strip; every
-      //      wave runs the exact FILTER of every WV-th listed label on the staged labelling -- read-only work, so the verdicts
-      //      are those of the sequential order as long as nothing has moved --; then wave 0 alone runs the DPs of the flagged
-      //      labels in ascending order.  The first DP that moves a cell makes every later verdict stale: from there on wave 0
-      //      continues as the one-wave kernel does, filtering every later label again (the memo entries the other waves
-      //      wrote for those labels are overwritten by that second look: its stores come after theirs, fence + barrier).
-      //      Label for label the launch is the one-wave launch.
-      const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-      if (wave == 0) stage_strip();
-      staged = true;
-      __syncthreads();
-      unsigned long long mine = 0ull;
-      {
-        unsigned long long t = todo;
-        int i = 0;
-        while (t) {
-          const int a = __ffsll((long long)t) - 1;
-          t &= t - 1ull;
-          if ((i++ % WV) == wave) mine |= 1ull << a;
-        }
-      }
-      unsigned long long left = 0ull;
-      if (mine) {
-        left = filter_phase<ORIENT, WV>(g, lds, lane, rs0, ca, ncols, ncell, valid[0], valid[1], valid[2], valid[3], valid[4], mine, n,
-                                        uT, mrow, tick0, peel_max, wave);
-        left = ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(left >> 32)) << 32) |
-               (unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)left);
-      } else if (lane == 0) {
-        lds_pool.nbuf[wave] = 0;
-      }
-      if (lane == 0) lds_pool.left[wave] = left;
-      __threadfence();
-      __syncthreads();
-      unsigned long long rest = 0ull;
-      if (wave == 0) {
-        // labels nobody has looked at (a wave's buffer of flagged labels was full: rare) bound the merged pass from above
-        unsigned long long unl = 0ull;
-#pragma unroll
-        for (int w = 0; w < WV; ++w) unl |= lds_pool.left[w];
-        unl = ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(unl >> 32)) << 32) |
-              (unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)unl);
-        const int cut = unl ? __ffsll((long long)unl) - 1 : 64;
-        int head[WV], cnt[WV];
-#pragma unroll
-        for (int w = 0; w < WV; ++w) {
-          head[w] = 0;
-          cnt[w] = __builtin_amdgcn_readfirstlane(lds_pool.nbuf[w]);
-        }
-        rest = cut < 64 ? (todo & ~((1ull << cut) - 1ull)) : 0ull;
-        for (;;) {
-          int bw = -1, ba = 64;
-#pragma unroll
-          for (int w = 0; w < WV; ++w)
-            if (head[w] < cnt[w]) {
-              const int a = __builtin_amdgcn_readfirstlane(lds_pool.abuf[w * NBUF + head[w]]);
-              if (a < ba) {
-                ba = a;
-                bw = w;
-              }
-            }
-          if (bw < 0 || ba >= cut) break;
-          int kb = 0;
-#pragma unroll
-          for (int w = 0; w < WV; ++w)
-            if (w == bw) kb = w * NBUF + head[w]++;
-          const unsigned int my_changed = dp_flagged<ORIENT, false, WV>(g, lds, kb, lane, rs0, ca, ncols, ncell, ba, tick0 + ba, n, D, nbr, uT,
-                                                                        labels, stamp, mrow ? mrow + ba : nullptr, changed + ba);
-          if (my_changed) {
-            __threadfence();
-            rest = todo_full & ~((2ull << ba) - 1ull);
-            break;
-          }
-        }
-        __builtin_amdgcn_wave_barrier();
-      }
-      todo = rest;                             // (waves 1 .. WV - 1: nothing; wave 0: what is left for the sequential loop)
-    }
 
     while (todo) {
       if (!staged) {
-        stage_strip();
+        // ---- staging (as strip_kernel, step A): labels and forward weights of the strip's rectangle and rim -> LDS
+        constexpr int NEP = (ECELLS + 63) / 64;
+        int enode[NEP], eidx[NEP];
+#pragma unroll
+        for (int q = 0; q < NEP; ++q) {
+          int er, ec;
+          if (ORIENT == 0) {
+            int l2 = lane;
+            asm volatile("" : "+v"(l2));
+            er = q < EH ? q : l2;
+            ec = q < EH ? l2 : 64;
+            if (q >= EH && l2 >= EH) ec = 1 << 20;
+          } else {
+            int e = q * 64 + lane;
+            asm volatile("" : "+v"(e));
+            ec = e / EH;
+            er = e - ec * EH;
+          }
+          const bool have = ec < ncols + 2;
+          eidx[q] = have ? ec * EH + er : -1;
+          enode[q] = have ? strip_node(g, rs0 - 1 + er, ca - 1 + ec) : -1;
+        }
+        int elab[NEP];
+        float4 ef[NEP];
+#pragma unroll
+        for (int q = 0; q < NEP; ++q) {
+          const int node = enode[q];
+          elab[q] = 0;
+          ef[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (node >= 0) {
+            elab[q] = labels[node];
+            ef[q] = fwd_w[node];
+          }
+        }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int q = 0; q < NEP; ++q) {
+          const int e = eidx[q];
+          if (e >= 0) {
+            const int ec = e / EH, er = e - ec * EH;
+            float* wr = slabw + ec * SWC + er * 4;
+            if (er < EH - 1) {
+              wr[0] = ef[q].x * beta;
+              wr[1] = ef[q].y * beta;
+              wr[2] = ef[q].z * beta;
+              wr[3] = ef[q].w * beta;
+            } else {
+              // the bottom rim row holds one edge the strip needs, and only in orientation 1: its cells' grid edge (+1, -1),
+              // which runs to strip row 4 of the next column; it lives in the column's 25th word
+              wr[0] = ef[q].y * beta;
+            }
+            slabl[e] = (unsigned char)(enode[q] >= 0 ? elab[q] : 0);
+          }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (lane == 0) {
+#if !defined(PHMRF_PHASE_CLOCK) && !defined(PHMRF_FILTER_STATS)
+          atomicAdd(&wk[2], (unsigned int)(EH * (ncols + 2)));
+          atomicAdd(&wk[4], (unsigned int)ncell);
+#endif
+        }
         staged = true;
       }
 
       PH(2)
-      todo = filter_phase<ORIENT, WV>(g, lds, lane, rs0, ca, ncols, ncell, valid[0], valid[1], valid[2], valid[3], valid[4], todo, n, uT,
-                                      mrow, tick0, peel_max, 0);
+      todo = filter_phase<ORIENT>(g, lds, lane, rs0, ca, ncols, ncell, valid[0], valid[1], valid[2], valid[3], valid[4], todo, n, uT,
+                                  mrow, tick0, peel_max);
       todo = ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(todo >> 32)) << 32) |
              (unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)todo);
       PH(0)
@@ -1869,12 +1661,12 @@ __global__ __launch_bounds__(64 * WV, PHMRF_COLS_WPE) void strip_cols_kernel(Str
 #ifdef PHMRF_COLS_NO_DP            // development: the filter alone (timing / register experiments; the labelling is wrong)
       const int nbuf = 0;
 #else
-      const int nbuf = __builtin_amdgcn_readfirstlane(lds_pool.nbuf[0]);
+      const int nbuf = __builtin_amdgcn_readfirstlane(lds_pool.nbuf);
 #endif
       for (int kb = 0; kb < nbuf; ++kb) {
         const int alpha = __builtin_amdgcn_readfirstlane(abuf[kb]);
-        const unsigned int my_changed = dp_flagged<ORIENT, false, WV>(g, lds, kb, lane, rs0, ca, ncols, ncell, alpha, tick0 + alpha, n, D, nbr,
-                                                                      uT, labels, stamp, mrow ? mrow + alpha : nullptr, changed + alpha);
+        const unsigned int my_changed = dp_flagged<ORIENT, false>(g, lds, kb, lane, rs0, ca, ncols, ncell, alpha, tick0 + alpha, n, D, nbr,
+                                                                  uT, labels, stamp, mrow ? mrow + alpha : nullptr, changed + alpha);
         PH(4)
         if (my_changed) {
           // the labels of this strip have changed: everything later is filtered again on the new labelling (the slab's
@@ -1883,15 +1675,12 @@ __global__ __launch_bounds__(64 * WV, PHMRF_COLS_WPE) void strip_cols_kernel(Str
 #ifdef PHMRF_COLS_RESTAGE
           staged = false;
 #endif
-          // (every later label the memo left -- those the seed masks had settled, too: the masks are those of the labels
-          //  before the move)
           todo = todo_full & ~((2ull << alpha) - 1ull);
           break;
         }
       }
       __builtin_amdgcn_wave_barrier();
     }
-    if constexpr (WV > 1) __syncthreads();       // (the strip's LDS is free for the workgroup's next strip)
   }
 #ifdef PHMRF_PHASE_CLOCK
   // slots: 0 pairs + 4096 x general sweeps, 1 extraction, 2 ids/memo/staging, 3 single-site costs, 4 DP, 5 sweeps
@@ -1906,7 +1695,9 @@ __global__ __launch_bounds__(64 * WV, PHMRF_COLS_WPE) void strip_cols_kernel(Str
   __syncthreads();
   if (work && threadIdx.x < WORK_SLOTS) {
     const unsigned int v = wk[threadIdx.x];
-    if (v) atomicAdd(work + (blockIdx.x & (WORK_BANKS - 1)) * WORK_SLOTS + threadIdx.x, (unsigned long long)v);
+    // (the workgroup id from its SGPR: blockIdx.x is a VGPR that stays live across the strip loop, and at this kernel's
+    //  128-VGPR budget the allocator spills it to scratch)
+    if (v) atomicAdd(work + (__builtin_amdgcn_workgroup_id_x() & (WORK_BANKS - 1)) * WORK_SLOTS + threadIdx.x, (unsigned long long)v);
   }
 }
 
@@ -1934,8 +1725,7 @@ __global__ __launch_bounds__(64, PHMRF_FUSION_WPE) void fusion_cols_kernel(Strip
                                                                           const float* __restrict__ sgain, float beta,
                                                                           unsigned long long* __restrict__ changed,
                                                                           uint16_t* __restrict__ stamp, uint16_t* __restrict__ memo,
-                                                                          int tick, unsigned long long* __restrict__ work, int peel_max,
-                                                                          const unsigned long long* __restrict__ scan) {
+                                                                          int tick, unsigned long long* __restrict__ work, int peel_max) {
   __shared__ FusLds lds_pool;
   float* slabw = lds_pool.c.slabw;
   unsigned char* slabl = lds_pool.c.slabl;
@@ -1949,9 +1739,7 @@ __global__ __launch_bounds__(64, PHMRF_FUSION_WPE) void fusion_cols_kernel(Strip
 
   const int nslots = strip_slots(ORIENT, g.nbands, g.nsegs, g.xcd);      // (the XCD-aware order of orientation 1: strip_of_slot)
   for (int slot_v = blockIdx.x; slot_v < nslots; slot_v += gridDim.x) {
-    const int slot_u = __builtin_amdgcn_readfirstlane(slot_v);
-    if (scan && !scan[2 * (int64_t)slot_u + 1]) continue;      // (strip_scan_kernel: the memo entry is newer than every stamp)
-    const int strip = strip_of_slot<ORIENT>(g, slot_u);
+    const int strip = strip_of_slot<ORIENT>(g, __builtin_amdgcn_readfirstlane(slot_v));
     if (strip < 0 || strip >= nstrips) continue;
     const int bnd = strip / g.nsegs;
     const int seg = strip - bnd * g.nsegs;
@@ -1970,7 +1758,7 @@ __global__ __launch_bounds__(64, PHMRF_FUSION_WPE) void fusion_cols_kernel(Strip
     uint16_t* mslot = memo ? memo + (int64_t)strip * (K + 1) + K : nullptr;
 #pragma unroll
     for (int r = 0; r < SH; ++r) ndx[r] = lane < ncols ? strip_node(g, rs0 + r, ca + lane) : -1;
-    if (mslot && !scan) {
+    if (mslot) {
       const int last_quiet = *mslot;
       if (last_quiet) {
         int nw = 0;
@@ -2221,8 +2009,7 @@ __global__ __launch_bounds__(256) void propose_grid_kernel(const float* __restri
                                                            int diagonal, const float4* __restrict__ fwd_w,
                                                            const uint8_t* __restrict__ labels, float beta,
                                                            uint8_t* __restrict__ prop, const uint16_t* __restrict__ stamp,
-                                                           int since, unsigned long long* __restrict__ work, float* __restrict__ sgain,
-                                                           unsigned long long* __restrict__ seed) {
+                                                           int since, unsigned long long* __restrict__ work, float* __restrict__ sgain) {
   extern __shared__ float tile[];
   const int TB = blockDim.x;
   unsigned int done = 0u;
@@ -2264,33 +2051,6 @@ __global__ __launch_bounds__(256) void propose_grid_kernel(const float* __restri
       }
       prop[v] = (uint8_t)bk;
       if (sgain) sgain[v] = bk != cur ? best - row[cur] : 1.0e30f;
-      if (seed) {
-        // SEED MASK (round 6): bit a = "an improving expansion of label a on a strip could start at this node".  The strip
-        // filter (peel_row) calls cell i a seed of label a when  s_i(a) < cap_i / 2,  s_i(a) = u_i(a) - u_i(l) + beta (h(l) - h(a))
-        // = row[a] - row[l] here, cap_i = the discounts w (2 - [l != l_j]) of i's in-strip neighbours still in U.  cap_i is at
-        // most V = sum over ALL eight neighbours, so  row[a] - row[l] < V / 2  is implied by the filter's test whatever the
-        // strip, the cut and the pass; the margins (1.0002 V + 4e-5 against the filter's 1.0001 cap + 2e-5; 2e-6 of the
-        // magnitudes against the <= 19 roundings of the two sums) keep that true in f32.  A (strip, label) pair none of
-        // whose cells has the bit is quiet without a look at the label's unary terms (strip_scan_kernel).
-        float vtot = 0.f;
-#pragma unroll
-        for (int d = 0; d < 8; ++d) {
-          const float bw = beta * nw[d];
-          vtot += nl[d] == cur ? bw + bw : bw;
-        }
-        const float rc = row[cur];
-        const float lim = rc + 0.5f * __builtin_fmaf(vtot, 1.0002f, 4e-5f) + 2e-6f * (fabsf(rc) + 2.f * vtot);
-        unsigned int mlo = 0u, mhi = 0u;
-        for (int k = 0; k < K && k < 32; ++k) {
-          const float x = row[k];
-          mlo |= (k != cur && __builtin_fmaf(fabsf(x), -2e-6f, x) < lim) ? (1u << k) : 0u;
-        }
-        for (int k = 32; k < K; ++k) {
-          const float x = row[k];
-          mhi |= (k != cur && __builtin_fmaf(fabsf(x), -2e-6f, x) < lim) ? (1u << (k - 32)) : 0u;
-        }
-        seed[v] = ((unsigned long long)mhi << 32) | (unsigned long long)mlo;
-      }
     }
   }
   {   // nodes recomputed by this workgroup (per-thread counts -> one add per wave)
@@ -2304,10 +2064,6 @@ __global__ __launch_bounds__(256) void propose_grid_kernel(const float* __restri
 inline int vec_of(int K) { return (K % 4 == 0) ? 4 : (K % 2 == 0 ? 2 : 1); }
 
 }  // namespace
-
-#ifdef PHMRF_DEV
-constexpr int PAR_DIRTY_DEFAULT = 0;      // launch_strip_multi (development builds): four waves per strip below this many (estimated) dirty strips; 0 = never
-#endif
 
 // Development knobs (read from the environment) exist only in builds with -DPHMRF_DEV (tools/variant.sh): the product
 // library has none that can change or break a labelling.
@@ -2330,52 +2086,23 @@ static int peel_sweeps() {   // PHMRF_PEEL_SWEEPS=0 switches the filter off (tim
   }
   return v;
 }
-static bool scan_enabled() {        // PHMRF_SCAN=1: strip_scan_kernel in front of every strip launch of a solve (a measured negative,
-  static const bool on = PHMRF_DEV_ENV("PHMRF_SCAN") != nullptr || PHMRF_DEV_ENV("PHMRF_SEED_MASKS") != nullptr;   // DESIGN.md 3.2)
-  return on;
-}
-static int mopup_grid() {           // PHMRF_MOPUP_GRID=n: workgroups of a strip launch in the rounds after a solve's first (0: one per slot)
-  static int v = -2;
-  if (v == -2) {
-    const char* e = PHMRF_DEV_ENV("PHMRF_MOPUP_GRID");
-    v = e ? atoi(e) : -1;
-  }
-  return v;
-}
-static bool seed_masks_enabled() {  // PHMRF_SEED_MASKS=1: the scan also uses the seed masks (a measured negative, DESIGN.md 3.2: kept
-  static const bool on = PHMRF_DEV_ENV("PHMRF_SEED_MASKS") != nullptr;   // for the A/B -- the labellings must not differ)
-  return on;
-}
-static int par_dirty_limit() {      // PHMRF_PAR_DIRTY=n: four waves per strip while the estimated dirty strips of a launch are <= n (0: never)
-  static int v = -2;
-  if (v == -2) {
-    const char* e = PHMRF_DEV_ENV("PHMRF_PAR_DIRTY");
-    v = e ? atoi(e) : PAR_DIRTY_DEFAULT;
-  }
-  return v;
-}
 #else
 static constexpr int strip_debug() { return 0; }
 static constexpr int peel_sweeps() { return PEEL_MAX; }
-static constexpr bool scan_enabled() { return false; }
-static constexpr int mopup_grid() { return -1; }
-static constexpr bool seed_masks_enabled() { return false; }
 #endif
 
 int launch_propose(phmrf_block* b, float beta) {
   const int since = b->tick ? b->prop_tick : -1;
   if (!b->sgain) PHMRF_HIP(hipMalloc(reinterpret_cast<void**>(&b->sgain), (size_t)b->n * sizeof(float)));
-  if (!b->seed && seed_masks_enabled()) PHMRF_HIP(hipMalloc(reinterpret_cast<void**>(&b->seed), (size_t)b->n * sizeof(unsigned long long)));
   const int K = b->K, TB = tile_threads(K), Kp = padded_k(K);
   const size_t lds = (size_t)TB * Kp * sizeof(float);
   int64_t g64 = (b->n + TB - 1) / TB;
   const int grid = (int)(g64 > 256 * 16 ? 256 * 16 : g64);
   if (b->has_grid && b->fwd_w && b->uT && b->uT_valid && b->D == 8) {
     hipLaunchKernelGGL(propose_grid_kernel, dim3(grid), dim3(TB), lds, b->stream, b->uT, b->n, K, Kp, b->H, b->W, b->diagonal,
-                       b->fwd_w, b->labels, beta, b->labels_tmp, b->stamp, since, b->work_acc, b->sgain, b->seed);
+                       b->fwd_w, b->labels, beta, b->labels_tmp, b->stamp, since, b->work_acc, b->sgain);
     PHMRF_HIP(hipGetLastError());
     b->prop_tick = b->tick ? b->tick : -1;
-    b->seed_tick = b->prop_tick;             // (the masks are those of the labelling at this tick; -1: not inside a solve)
     return PHMRF_OK;
   }
 #define PHMRF_LAUNCH_PROP(VEC_)                                                                                     \
@@ -2389,7 +2116,6 @@ int launch_propose(phmrf_block* b, float beta) {
 #undef PHMRF_LAUNCH_PROP
   PHMRF_HIP(hipGetLastError());
   b->prop_tick = b->tick ? b->tick : -1;
-  b->seed_tick = -1;                         // (the adjacency form writes no seed masks)
   return PHMRF_OK;
 }
 
@@ -2408,19 +2134,6 @@ static StripGeom make_geom(const phmrf_block* b, int orient, int shift_r, int sh
   static const bool plain_order = PHMRF_DEV_ENV("PHMRF_NO_XCD_MAP") != nullptr;      // development: A/B of the strips' order
   g.xcd = plain_order ? 0 : 1;
   return g;
-}
-
-// how many strip slots a launch on this block can have at most (either orientation, any cut): the size of scan_out
-int64_t strip_scan_slots(const phmrf_block* b) {
-  int64_t m = 0;
-  for (int orient = 0; orient < 2; ++orient) {
-    const int Hs = orient ? b->W : b->H, Ws = orient ? b->H : b->W;
-    const int nbands = (Hs + 5 + SH) / (SH + 1), nsegs = (Ws + 63 + 63) / 64;
-    const int64_t a = strip_slots(orient, nbands, nsegs, 1), c = (int64_t)nbands * nsegs;
-    m = a > m ? a : m;
-    m = c > m ? c : m;
-  }
-  return m;
 }
 
 int launch_unary_planes(phmrf_block* b) {
@@ -2454,27 +2167,13 @@ int launch_strip_pass(const phmrf_block* b, float beta, int orient, int shift_r,
   // the fusion pass of a solve (proposals in labels_tmp) runs behind the exact filter (fusion_cols_kernel); the
   // single-label passes of the API and the coarse child problems keep strip_kernel.
   if (alpha < 0) {
-    const int fslots = strip_slots(orient, g.nbands, g.nsegs, g.xcd);
-    int fgrid = fslots;
+    int fgrid = strip_slots(orient, g.nbands, g.nsegs, g.xcd);
     if (fgrid > (1 << 22)) fgrid = 1 << 22;
-    if (b->ss && b->ss->rounds > 0 && mopup_grid() > 0 && fgrid > mopup_grid()) fgrid = mopup_grid();
     uint16_t* const fmemo = use_memo ? b->memo + ((int64_t)(orient * 3 + geom) * b->memo_strips) * (b->K + 1) : nullptr;
-    // inside a solve the strips' stamps and memo entries are looked at by a light kernel of their own (strip_scan_kernel)
-    const bool use_scan = use_memo && b->scan_out && (int64_t)fslots <= b->scan_slots && scan_enabled();
-    if (use_scan) {
-#define PHMRF_LAUNCH_FSCAN(O_)                                                                                        \
-  hipLaunchKernelGGL((strip_scan_kernel<O_, true>), dim3((fslots + 3) / 4), dim3(256), 0, b->stream, g, b->K, 0ull, b->stamp, fmemo, \
-                     b->tick, static_cast<const unsigned long long*>(nullptr), -1, b->scan_out, b->work_acc)
-      if (orient) PHMRF_LAUNCH_FSCAN(1);
-      else PHMRF_LAUNCH_FSCAN(0);
-#undef PHMRF_LAUNCH_FSCAN
-      PHMRF_HIP(hipGetLastError());
-    }
 #define PHMRF_LAUNCH_FUSION(O_)                                                                                       \
   hipLaunchKernelGGL((fusion_cols_kernel<O_>), dim3(fgrid), dim3(64), 0, b->stream, g, b->n, b->K, b->D, b->nbr, b->fwd_w,  \
                      b->uT, b->labels, b->labels_tmp, b->sgain, beta, b->counters + b->counter_slot,                   \
-                     b->tick ? b->stamp : nullptr, fmemo, b->tick, b->work_acc, peel_sweeps(),                        \
-                     use_scan ? b->scan_out : static_cast<const unsigned long long*>(nullptr))
+                     b->tick ? b->stamp : nullptr, fmemo, b->tick, b->work_acc, peel_sweeps())
     if (orient) PHMRF_LAUNCH_FUSION(1);
     else PHMRF_LAUNCH_FUSION(0);
 #undef PHMRF_LAUNCH_FUSION
@@ -2516,53 +2215,16 @@ int launch_strip_multi(const phmrf_block* b, float beta, int orient, int shift_r
   // one workgroup per strip (orientation 1: per slot of the XCD-aware order, strip_of_slot) up to 4 M: the dispatcher hands a
   // free slot the next strip, which balances the uneven strips better than waves striding over them (measured against a cap
   // of 8 resident sets: -3 % on the rows cut)
-  const int nslots = strip_slots(orient, g.nbands, g.nsegs, g.xcd);
-  int grid = nslots;
+  int grid = strip_slots(orient, g.nbands, g.nsegs, g.xcd);
   if (grid > (1 << 22)) grid = 1 << 22;
-  if (b->ss && b->ss->rounds > 0 && mopup_grid() > 0 && grid > mopup_grid()) grid = mopup_grid();
   const bool use_memo = b->tick && geom >= 0 && b->memo && (int64_t)nstrips <= b->memo_strips;
   uint16_t* const mmemo = use_memo ? b->memo + ((int64_t)(orient * 3 + geom) * b->memo_strips) * (b->K + 1) : nullptr;
-  // inside a solve: strip_scan_kernel first -- stamps against the memo, and the seed masks of the proposals' launch where
-  // they are current (b->seed_tick: launch_propose on a grid block in this solve)
-  const bool use_scan = use_memo && b->scan_out && (int64_t)nslots <= b->scan_slots && scan_enabled();
-  if (use_scan) {
-    const bool masks = b->seed && b->seed_tick >= 0 && seed_masks_enabled();
-#define PHMRF_LAUNCH_SCAN(O_)                                                                                         \
-  hipLaunchKernelGGL((strip_scan_kernel<O_, false>), dim3((nslots + 3) / 4), dim3(256), 0, b->stream, g, b->K, label_mask, b->stamp, \
-                     mmemo, b->tick, masks ? b->seed : static_cast<const unsigned long long*>(nullptr), b->seed_tick,   \
-                     b->scan_out, b->work_acc)
-    if (orient) PHMRF_LAUNCH_SCAN(1);
-    else PHMRF_LAUNCH_SCAN(0);
-#undef PHMRF_LAUNCH_SCAN
-    PHMRF_HIP(hipGetLastError());
-  }
-  // (round 6, development builds only: a measured negative) FOUR WAVES PER STRIP in a solve's late rounds,
-  // PHMRF_PAR_DIRTY=n: when the previous round changed so few labels that the dirty strips (estimated from the round's change
-  // count) are <= n, four waves share the staged strip and split the labels' filters (strip_cols_kernel, WV = 4).  Same
-  // labelling, label for label -- and no faster: a four-wave workgroup takes a quarter of the GPU's strip slots.
-  bool four_waves = false;
-#ifdef PHMRF_DEV
-  if (use_memo && b->ss && b->ss->rounds > 0 && par_dirty_limit() > 0) {
-    const int64_t est_dirty = std::min<int64_t>((int64_t)nstrips, 2 * b->ss->last_changed);
-    four_waves = est_dirty <= par_dirty_limit();
-  }
-#endif
-#define PHMRF_LAUNCH_MULTI(O_, W_)                                                                                    \
-  hipLaunchKernelGGL((strip_cols_kernel<O_, W_>), dim3(grid), dim3(TB * W_), 0, b->stream, g, b->n, b->K, b->D, b->nbr, b->fwd_w, \
+#define PHMRF_LAUNCH_MULTI(O_)                                                                                        \
+  hipLaunchKernelGGL((strip_cols_kernel<O_>), dim3(grid), dim3(TB), 0, b->stream, g, b->n, b->K, b->D, b->nbr, b->fwd_w, \
                      b->uT, b->labels, beta, label_mask, b->counters + 8, b->tick ? b->stamp : nullptr, mmemo,          \
-                     b->tick, b->work_acc, peel_sweeps(),                                                             \
-                     use_scan ? b->scan_out : static_cast<const unsigned long long*>(nullptr))
-#ifdef PHMRF_DEV
-  if (four_waves) {
-    if (orient) PHMRF_LAUNCH_MULTI(1, 4);
-    else PHMRF_LAUNCH_MULTI(0, 4);
-  } else
-#endif
-  {
-    (void)four_waves;
-    if (orient) PHMRF_LAUNCH_MULTI(1, 1);
-    else PHMRF_LAUNCH_MULTI(0, 1);
-  }
+                     b->tick, b->work_acc, peel_sweeps())
+  if (orient) PHMRF_LAUNCH_MULTI(1);
+  else PHMRF_LAUNCH_MULTI(0);
 #undef PHMRF_LAUNCH_MULTI
   PHMRF_HIP(hipGetLastError());
   return PHMRF_OK;

@@ -965,72 +965,6 @@ def test_coarse_shortcuts_leave_the_labellings_alone():
     assert runs[0][1] >= 3
 
 
-SEED_SCRIPT = r"""
-import os, sys, hashlib
-import numpy as np
-sys.path.insert(0, os.environ["PHMRF_ROOT"])
-import torch
-from phylo_hmrf_amd import Block, synthetic
-from phylo_hmrf_amd.tree import PhyloTree
-K, S, N = 12, 4, 700
-tree = PhyloTree(synthetic.tree_for(S)); rng = np.random.default_rng(4)
-P = synthetic.sample_ou_params(rng, tree, K); mu, cv = tree.mean_cov(P); cv = cv + 1e-3 * np.eye(S)
-P2 = np.clip(P * (1 + 0.15 * rng.standard_normal(P.shape)), 1e-3, 50); mu2, cv2 = tree.mean_cov(P2); cv2 = cv2 + 1e-3 * np.eye(S)
-P3 = np.clip(P2 * (1 + 0.05 * rng.standard_normal(P.shape)), 1e-3, 50); mu3, cv3 = tree.mean_cov(P3); cv3 = cv3 + 1e-3 * np.eye(S)
-dev = torch.device("cuda", 0)
-X = synthetic.device_observations(torch, dev, 2, N, N, True, K, mu, cv); torch.cuda.synchronize()
-n = N * (N + 1) // 2
-b = Block(n, S, K); b.set_observations_dev(X.data_ptr()); b.sync(); b.build_grid_graph(N, N, True, 8, 0.5)
-b.enable_timing(True); b.reset_timing()
-out = []
-b.emission(mu2, cv2)
-res = b.solve(1.0, energy_tol_ppb=1000, init_mode=1)              # cold
-out.append((hashlib.sha1(b.get_labels().tobytes()).hexdigest(), res["rounds"], repr(res["energy"])))
-b.emission(mu3, cv3)
-res = b.solve(1.0, energy_tol_ppb=1000)                           # warm, as an EM iteration's E-step
-out.append((hashlib.sha1(b.get_labels().tobytes()).hexdigest(), res["rounds"], repr(res["energy"])))
-res = b.solve(1.0, energy_tol_ppb=0)                              # to the exact fixed point of every move type
-out.append((hashlib.sha1(b.get_labels().tobytes()).hexdigest(), res["rounds"], repr(res["energy"])))
-w = b.work()
-print("RESULT", (out, w["mask_label_cells"], w["mask_strip_cells"], w["label_cells"]))
-"""
-
-
-def test_strip_scan_and_seed_masks_leave_the_labellings_alone():
-    """Round 6: strip_scan_kernel looks at every strip's stamps and memo row BEFORE the strip launch (two words per strip
-    slot; the launch's workgroup returns after one scalar load where there is nothing to do).  Exact: with
-    PHMRF_DETERMINISTIC=1 a cold solve, a warm solve and a solve to the exact fixed point give the same label hashes, round
-    counts and energies (a) as shipped -- every strip reading its own stamps and memo row --, (b) with the scan in front of
-    every strip launch (PHMRF_SCAN=1) and (c) with the SEED MASKS on top of the scan (PHMRF_SEED_MASKS=1): per-node bits "an improving
-    expansion of label a could start here" written by the proposals' launch, a superset of the filter's own first-pass seed
-    test, OR-ed over a strip by the scan.  (c) is exact, too, but settles little -- the fusion pass and the other orientation's
-    expansions run between the proposals' launch and the strip launch and leave a stamp in nearly every strip, which voids
-    the strip's masks; and (b) costs what it saves, the floor of a mop-up launch being one wave's walk through its strip's
-    labels, not the look at the stamps -- so both are development options, off in the product."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    dev = os.path.join(root, "phylo_hmrf_amd", "libphmrf_dev.so")      # (the knobs exist in the -DPHMRF_DEV build only)
-    assert os.path.exists(dev), "libphmrf_dev.so not built (make -C phylo_hmrf_amd/csrc)"
-    runs = []
-    # (d) round 6, development option: FOUR WAVES PER STRIP in a solve's late rounds (strip_cols_kernel<orient, 4>: the labels'
-    #     filters of a dirty strip on four waves, the rare DPs in label order on one; PHMRF_PAR_DIRTY=100000: every round after
-    #     a solve's first).  Exact as well, and no faster (DESIGN.md 3.2): the product keeps one wave per strip.
-    for extra in ({}, {"PHMRF_SCAN": "1", "PHMRF_LIB": dev}, {"PHMRF_SEED_MASKS": "1", "PHMRF_LIB": dev},
-                  {"PHMRF_PAR_DIRTY": "100000", "PHMRF_LIB": dev}):
-        env = dict(os.environ, PHMRF_ROOT=root, PHMRF_DETERMINISTIC="1", **extra)
-        out = subprocess.run([sys.executable, "-c", SEED_SCRIPT], capture_output=True, text=True, timeout=600, env=env)
-        assert out.returncode == 0, out.stderr[-3000:]
-        line = [ln for ln in out.stdout.splitlines() if ln.startswith("RESULT")][-1]
-        runs.append(eval(line[len("RESULT"):]))
-    assert runs[0][0] == runs[1][0] == runs[2][0] == runs[3][0], runs
-    assert runs[0][1] == 0 and runs[1][1] == 0 and runs[3][1] == 0   # no masks: nothing settled by them
-    assert runs[0][3] == runs[1][3]                                  # the same (strip, label) pairs went through the filter
-    settled, examined = runs[2][1], runs[2][3]
-    # the same pairs, decided one way or the other (a label the masks settled is looked at again after a move on its strip)
-    assert settled > 0 and runs[0][3] <= settled + examined <= 1.05 * runs[0][3], runs
-
-
 GROUP_SCRIPT = r"""
 import os, sys, hashlib
 import numpy as np
