@@ -205,18 +205,33 @@ PHMRF_API int phmrf_mrf_solve_group(phmrf_block_t* blocks, int n_blocks, double 
 /* The same solve in pieces (phmrf_mrf_solve is exactly begin; {launch; collect; decide} while *status == 0; end):
  *   begin    resets the solve's state (stamps, memos, schedule); want_init_energy: also evaluate the starting energy
  *   launch   queues one round's kernels and the read-back of its change counters and energy on the block's stream
- *   collect  waits for them: counters[128] (changes per move type, the slots of phmrf_mrf_solve) and
+ *   collect  waits for them: counters[PHMRF_NUM_COUNTERS] (labels changed per move type, the slots below) and
  *            energy[2] = (unary sum, pair sum without beta) after the round
  *   decide   runs the schedule on (counters, energy) -- this block's, or the SUMS over the row tiles of one block that
  *            live in different blocks / on different GPUs, which then all take the same decisions --;
  *            *status: 0 another round, 1 converged, 2 stopped by max_rounds or the launch budget
  *   end      fills res (may be NULL) and ends the solve.
  * Replaces, with phmrf_block_set_tile, the reference's one-process-per-block loop (base.py:357-372) for blocks that are
- * larger than one GPU's share. */
+ * larger than one GPU's share.
+ * The slots of `counters` a caller may rely on (labels changed in the round by ...); every other slot is the library's own
+ * and reads 0 or a number without meaning for the caller:
+ *   PHMRF_COUNTER_EXPANSION + a   the alpha-expansions of label a (a < 64)
+ *   PHMRF_COUNTER_CHAIN + f       chain family f (0 rows, 1 columns, 2 diagonals, 3 anti-diagonals; general graphs: path families)
+ *   PHMRF_COUNTER_ICM             the ICM sweep
+ *   PHMRF_COUNTER_COMPONENT       the component pass
+ *   PHMRF_COUNTER_FUSION + o      the strip fusion pass of orientation o (0, 1)
+ *   PHMRF_COUNTER_COARSE + lv     the coarse alpha-expansions of scale lv (0: 2 x 2, 1: 4 x 4, 2: 8 x 8 super-cells) */
+#define PHMRF_NUM_COUNTERS 128
+#define PHMRF_COUNTER_EXPANSION 8
+#define PHMRF_COUNTER_CHAIN 72
+#define PHMRF_COUNTER_ICM 76
+#define PHMRF_COUNTER_COMPONENT 77
+#define PHMRF_COUNTER_FUSION 78
+#define PHMRF_COUNTER_COARSE 80
 PHMRF_API int phmrf_mrf_solve_begin(phmrf_block_t b, double beta, const phmrf_solve_opts* opts, int want_init_energy);
 PHMRF_API int phmrf_mrf_solve_round_launch(phmrf_block_t b);
-PHMRF_API int phmrf_mrf_solve_round_collect(phmrf_block_t b, uint64_t* counters /*[128]*/, double* energy /*[2]*/);
-PHMRF_API int phmrf_mrf_solve_round_decide(phmrf_block_t b, const uint64_t* counters /*[128]*/, const double* energy /*[2]*/,
+PHMRF_API int phmrf_mrf_solve_round_collect(phmrf_block_t b, uint64_t* counters /*[PHMRF_NUM_COUNTERS]*/, double* energy /*[2]*/);
+PHMRF_API int phmrf_mrf_solve_round_decide(phmrf_block_t b, const uint64_t* counters /*[PHMRF_NUM_COUNTERS]*/, const double* energy /*[2]*/,
                                            int* status);
 PHMRF_API int phmrf_mrf_solve_end(phmrf_block_t b, phmrf_solve_result* res);
 

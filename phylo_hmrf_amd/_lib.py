@@ -13,6 +13,15 @@ LIB_PATH = os.environ.get("PHMRF_LIB") or os.path.join(_HERE, "libphmrf.so")
 OK = 0
 ABI_VERSION = 126             # include/phmrf.h PHMRF_VERSION: checked against the library in load()
 NUM_KERNEL_CLASSES = 10
+# the per-block counter bank of a solve's round (include/phmrf.h, PHMRF_NUM_COUNTERS and the PHMRF_COUNTER_* slots:
+# tests/test_abi.py holds the two sides together): labels changed per move type
+N_COUNTERS = 128
+COUNTER_EXPANSION = 8         # + label: its alpha-expansions
+COUNTER_CHAIN = 72            # + chain family
+COUNTER_ICM = 76
+COUNTER_COMPONENT = 77
+COUNTER_FUSION = 78           # + orientation
+COUNTER_COARSE = 80           # + coarse scale (2 x 2, 4 x 4, 8 x 8 super-cells)
 KERNEL_CLASSES = ("emission", "icm", "chain", "component", "energy", "posterior_stats", "strip", "propose", "coarse", "fusion")
 
 

@@ -4,7 +4,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import SolveOpts, SolveResult, as_f64, check, ptr_d, ptr_i32, ptr_i64
+from ._lib import N_COUNTERS, SolveOpts, SolveResult, as_f64, check, ptr_d, ptr_i32, ptr_i64
 
 
 class Block(object):
@@ -161,8 +161,8 @@ class Block(object):
         check(self._L.phmrf_mrf_solve_round_launch(self._h))
 
     def solve_round_collect(self):
-        """-> (counters uint64[128], energy float64[2] = unary sum, pair sum without beta) of this block after the round"""
-        c = np.zeros(128, dtype=np.uint64)
+        """-> (counters uint64[N_COUNTERS], energy float64[2] = unary sum, pair sum without beta) of this block after the round"""
+        c = np.zeros(N_COUNTERS, dtype=np.uint64)
         e = np.zeros(2, dtype=np.float64)
         check(self._L.phmrf_mrf_solve_round_collect(self._h, c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ptr_d(e)))
         return c, e

@@ -316,7 +316,7 @@ int launch_coarsen_batch(const phmrf_block* b, phmrf_block* const* children, con
     out.c_fwd[q] = child->fwd_w;
     out.c_labels[q] = child->labels;
     out.alpha[q] = q < nl ? alphas[q] : alphas[0];
-    out.c_counter[q] = (q < nl && reset) ? child->counters : nullptr;
+    out.c_counter[q] = (q < nl && reset) ? child->counters + child->counter_slot : nullptr;
   }
   out.moved_flag = reset ? b->coarse_flag : nullptr;
   out.nl = nl;

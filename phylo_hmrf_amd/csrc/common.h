@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <array>
 #include <string>
 #include <vector>
 
@@ -51,6 +52,33 @@ struct ChainFamily {
   int n_colours = 0;
   int max_len = 0;
 };
+
+// ---- the counter bank: phmrf_block::counters[N_COUNTERS], unsigned 64-bit, one bank per block -----------------------
+// A move launch adds the labels it changed to counters[b->counter_slot].  A round of the solver zeroes the bank, gives every
+// move type its own slot and reads the whole bank back once (solve.hip); the slots cross the ABI (phmrf.h: the macros
+// behind the constants below) and the tile conductor sums them over ranks, so THE NUMBERS STAY.
+constexpr int N_COUNTERS = PHMRF_NUM_COUNTERS;
+constexpr int MAX_LABELS = 64;                              // K <= 64 (phmrf_block_create)
+constexpr int MAX_CHAIN_FAMILIES = 4;                       // grid: rows, columns, diagonals, anti-diagonals; general graphs: four path families
+constexpr int N_COARSE = 3;                                 // coarse scales: super-cells of side 2, 4, 8
+constexpr int N_COARSE_CHILDREN = 4 * N_COARSE;             // child problems per block: [scale * 4 + slot in a batch of labels]
+constexpr int COUNTER_DEFAULT = 0;                          // outside a solve: what a single-pass entry point counts into and reads back
+                                                            // 1 .. 7: unused
+constexpr int COUNTER_EXPANSION = PHMRF_COUNTER_EXPANSION;  // + a: the alpha-expansions of label a
+constexpr int COUNTER_CHAIN = PHMRF_COUNTER_CHAIN;          // + f: chain family f
+constexpr int COUNTER_ICM = PHMRF_COUNTER_ICM;
+constexpr int COUNTER_COMPONENT = PHMRF_COUNTER_COMPONENT;
+constexpr int COUNTER_FUSION = PHMRF_COUNTER_FUSION;        // + orientation
+constexpr int COUNTER_COARSE = PHMRF_COUNTER_COARSE;        // + lv: coarse scale lv
+// development traces of the strip kernels (strips, not labels; a kernel gets the address of counters[COUNTER_TRACE] or null)
+constexpr int COUNTER_TRACE = 100;
+enum TraceCounter { TRACE_SEEN = 0, TRACE_PAST_MEMO = 1, TRACE_INTO_DP = 2, TRACE_DP_STEPS = 3, TRACE_MOVED = 4, N_TRACE = 5 };
+constexpr int COUNTER_ENERGY = 120;                         // [120], [121]: the round's (unary, pair) energy sums (energy_round_launch)
+static_assert(COUNTER_DEFAULT < COUNTER_EXPANSION && COUNTER_EXPANSION + MAX_LABELS <= COUNTER_CHAIN, "label slots run into the chain slots");
+static_assert(COUNTER_CHAIN + MAX_CHAIN_FAMILIES <= COUNTER_ICM && COUNTER_ICM < COUNTER_COMPONENT && COUNTER_COMPONENT < COUNTER_FUSION,
+              "chain / ICM / component slots overlap");
+static_assert(COUNTER_FUSION + 2 <= COUNTER_COARSE && COUNTER_COARSE + N_COARSE <= COUNTER_TRACE, "fusion / coarse slots overlap");
+static_assert(COUNTER_TRACE + N_TRACE <= COUNTER_ENERGY && COUNTER_ENERGY + 2 <= N_COUNTERS, "trace / energy slots do not fit the bank");
 
 }  // namespace phmrf
 
@@ -112,14 +140,14 @@ struct phmrf_block {
   bool uT_valid = false;                    //   ... current with logprob
   bool unary_pins = false;                  // a coarse child problem: unary terms >= 1e29 pin a cell (strip_kernel looks first)
   // coarse alpha-expansions (coarse.hip): child blocks holding the two-label problem of the super-cells, side 2, 4, 8
-  phmrf_block* coarse[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [level * 4 + slot in a batch of labels]
+  phmrf_block* coarse[phmrf::N_COARSE_CHILDREN] = {};   // [level * 4 + slot in a batch of labels]
   unsigned int* coarse_flag = nullptr;      // device: set by coarse_apply_kernel when a label of the batch has moved
   // coarse-to-fine start of a cold solve (c2f.hip): the block of C2F_SCALE x C2F_SCALE super-cells, a full block of its own
   phmrf_block* c2f = nullptr;
   int c2f_Hc = 0, c2f_Wc = 0;
-  unsigned long long* coarse_lab = nullptr;       // device [3][64]: labels changed per coarse scale and label in the round (the schedule rests labels)
+  unsigned long long* coarse_lab = nullptr;       // device [N_COARSE][MAX_LABELS]: labels changed per coarse scale and label in the round (the schedule rests labels)
   unsigned long long* coarse_lab_host = nullptr;  //   ... its pinned host mirror
-  char* coarse_arena = nullptr;             // ONE allocation behind the twelve child problems (labels, unary planes, weights, counters)
+  char* coarse_arena = nullptr;             // ONE allocation behind the child problems (labels, unary planes, weights, counters)
   // alpha-expansion of a graph that is no grid by a minimum cut (maxflow.hip): reverse-arc slots and the flow's state
   uint8_t* mf_rev = nullptr;                // device [n, D]: slot of arc (u -> v) in v's adjacency row
   float* mf_theta = nullptr;                // device [n]: a node's switch cost
@@ -141,14 +169,14 @@ struct phmrf_block {
   size_t chain_memo_count = 0;
   int64_t memo_strips = 0;
   int tick = 0;                             // host launch counter inside one solve (0 = stamping off)
-  int counter_slot = 0;                     // which of counters[128] the next move launches add their changes to
+  int counter_slot = 0;                     // which of counters[N_COUNTERS] the next move launches add their changes to
 
   float* emis_params = nullptr;             // device packed emission parameters
   float* posteriors = nullptr;              // device [n, K], allocated on demand
   char* summary = nullptr;                  // device [n] conf f32 | [n] entropy f32 | [n] top u8 (phmrf_posterior_summary), on demand
   double* accum = nullptr;                  // device small f64 accumulator area
   double* accum_host = nullptr;             // pinned mirror
-  unsigned long long* counters = nullptr;   // device [128]
+  unsigned long long* counters = nullptr;   // device [N_COUNTERS]: the counter bank (slots: above)
   unsigned long long* counters_host = nullptr;
   unsigned long long* work_acc = nullptr;   // device [WORK_BANKS][WORK_SLOTS], zeroed and read back with the counters
   unsigned long long* work_host = nullptr;  // pinned mirror
@@ -192,7 +220,7 @@ struct phmrf_block {
   struct phmrf_solve_state* ss = nullptr;   // a solve in progress (phmrf_mrf_solve_begin .. _end)
 };
 
-// the label solver between phmrf_mrf_solve_begin and _end (api.hip)
+// the label solver between phmrf_mrf_solve_begin and _end (solve.hip)
 struct phmrf_solve_state {
   phmrf_solve_opts o;
   double beta = 0;
@@ -207,17 +235,17 @@ struct phmrf_solve_state {
   int64_t sched_n = 0;
   std::vector<int> slots;
   int64_t last_changed = 0;            // labels changed by the previous round
-  int64_t coarse_changed[3] = {0, 0, 0};  // ... by the coarse scales in their last run
-  bool coarse_ran[3] = {false, false, false};
-  unsigned long long coarse_lab_mask[3] = {~0ull, ~0ull, ~0ull};   // the labels a coarse scale still runs (bit per label)
-  bool coarse_all[3] = {true, true, true};                         //   ... this round it ran all of them
+  int64_t coarse_changed[phmrf::N_COARSE] = {0, 0, 0};  // ... by the coarse scales in their last run
+  bool coarse_ran[phmrf::N_COARSE] = {false, false, false};
+  unsigned long long coarse_lab_mask[phmrf::N_COARSE] = {~0ull, ~0ull, ~0ull};   // the labels a coarse scale still runs (bit per label)
+  bool coarse_all[phmrf::N_COARSE] = {true, true, true};                         //   ... this round it ran all of them
   bool force_coarse = false;           // the tolerance wants to stop, but the coarse scales have not had their say
   bool coarse_checked = false;
-  std::vector<char> active, ran;
+  std::array<char, phmrf::N_COUNTERS> active{}, ran{};    // per counter slot: the move type is on / has run this round
   // labels changed by each move type in its LAST RUN (a type that did not run in a round -- chain families and ICM outside
   // verification rounds, the component pass in mop-up rounds, coarse scales that are off -- keeps that count: the resting
   // budget below must not read "did not run" as "changed nothing"); -1: has not run in this solve
-  std::vector<long long> last_count;
+  std::array<long long, phmrf::N_COUNTERS> last_count{};
   bool all_active = true, verifying = false;
   double eu_carry = 0, ep_carry = 0;   // (unary, pair without beta) at the last evaluation
   double e_prev = 0;
@@ -251,6 +279,44 @@ constexpr int ACCUM_DOUBLES = 8192;  // >= K*(1+S+S*S)+16 for every (K,S) the po
 // RAII-free helpers for the timers: call tic before the launches of one class, toc after.
 void tic(phmrf_block* b, int kclass);
 void toc(phmrf_block* b, int kclass, int n_launches);
+void resolve_timing(phmrf_block* b);    // waits for the stream and folds the pending event pairs into b->ms
+
+// ---- host helpers shared by api.hip (where they are defined unless inline) and solve.hip ------------------------------
+template <typename T>
+int dev_alloc(T** p, size_t count) {
+  *p = nullptr;
+  if (count == 0) count = 1;
+  PHMRF_HIP(hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
+  return PHMRF_OK;
+}
+
+template <typename T>
+void dev_free(T*& p) {
+  if (p) (void)hipFree(p);
+  p = nullptr;
+}
+
+inline bool is_tile(const phmrf_block* b) { return b->tile_top || b->tile_bot; }   // a row tile of a larger block (tile.hip)
+
+struct Geometry;                                                       // (row, col) of a node id under a block's geometry: below
+int setup_grid_tables(phmrf_block* b, const Geometry& g, int num_neighbor);   // ICM colours, chain families, forward weights
+int setup_path_families(phmrf_block* b);                               // chain families of a graph that is no grid
+int zero_accum(phmrf_block* b, size_t first, size_t count);
+int check_solvable(phmrf_block* b);
+int energy_now(phmrf_block* b, double beta, double* eu, double* ep);   // full evaluation, waits for the stream
+void energy_sums(const phmrf_block* b, const void* slots, double* eu, double* ep);   // an evaluation's two 8-byte slots -> (unary, pair without beta)
+int work_fetch_async(phmrf_block* b);
+void work_fold(phmrf_block* b, bool first_round = false);
+// one sweep of a move type into counters[b->counter_slot] (the caller zeroes and reads the bank)
+int icm_sweep_nocount(phmrf_block* b, float beta);
+int chain_sweep_nocount(phmrf_block* b, float beta, int family, int phase, bool timed = true);
+int strip_pass_nocount(phmrf_block* b, float beta, int orient, int shift_r, int shift_c, int alpha, int geom = -1, bool timed = true);
+// solve.hip
+int coarse_child(phmrf_block* b, int level_slot, phmrf_block** out);   // level_slot = level * 4 + slot in a batch
+void coarse_children_destroy(phmrf_block* b);
+int coarse_sweep_nocount(phmrf_block* b, float beta, int level, int off, int shift_r, int shift_c, int alpha_lo, int alpha_hi,
+                         unsigned long long label_mask = ~0ull);
+int tile_queue_boundary(phmrf_block* b);
 
 inline int tile_threads(int K) { return K <= 40 ? 256 : 128; }
 inline int padded_k(int K) { return (K % 2 == 0) ? K + 1 : K; }  // odd LDS row stride: conflict-free row-per-lane access
@@ -322,6 +388,8 @@ __host__ __device__ __forceinline__ I grid_node(int i, int j, int H, int W, int 
   if (i < 0 || i >= H || j < 0 || j >= W || (diagonal && i > j)) return -1;
   return grid_id<I>(i, j, W, diagonal);
 }
+// first node of grid row i of a block (i == H: n)
+inline int64_t row_first(const phmrf_block* b, int i) { return grid_row_first(i, b->W, b->diagonal); }
 __host__ __device__ __forceinline__ void grid_coords(int64_t v, int W, int diagonal, int* i, int* j) {
   if (!diagonal) {
     *i = (int)(v / W);
@@ -336,6 +404,16 @@ __host__ __device__ __forceinline__ void grid_coords(int64_t v, int W, int diago
   *i = r;
   *j = r + (int)(v - grid_row_first(r, W, 1));
 }
+
+// (row, col) of node id under the block geometry
+struct Geometry {
+  int H, W, diagonal;
+  explicit Geometry(int H_, int W_, int diag) : H(H_), W(W_), diagonal(diag) {}
+  int64_t count() const { return grid_row_first(H, W, diagonal); }
+  void coords(int64_t id, int* i, int* j) const { grid_coords(id, W, diagonal, i, j); }
+  int64_t id(int i, int j) const { return grid_row_base(i, W, diagonal) + j; }
+  bool valid(int i, int j) const { return i >= 0 && i < H && j >= 0 && j < W && (!diagonal || i <= j); }
+};
 
 // Ids c[8] of the eight neighbours of node v = (i, j) in the order of the adjacency rows (ascending ids: NW N NE W E SW S
 // SE); an absent neighbour is v itself.  Returns the mask of the present ones (bit d: c[d]).

@@ -20,7 +20,7 @@ constexpr int ACC_STATS = 8;   // accum[8..]   post | obs | obs*obs.T
 
 // The two energy sums of a workgroup.  Deterministic mode (PHMRF_DETERMINISTIC=1): as 2^-20 fixed-point integers in the
 // same 8-byte slots -- integer atomics commute, so the round-by-round energies the solver decides on are the same in
-// every run (the host converts back, api.hip energy_now).
+// every run (the host converts back: api.hip energy_now, solve.hip energy_round_collect).
 constexpr double ENERGY_FIX = 1048576.0;
 __device__ __forceinline__ void energy_flush(double* accum, double tu, double tp, int det) {
   if (det) {

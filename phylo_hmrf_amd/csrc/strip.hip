@@ -308,6 +308,8 @@ __global__ __launch_bounds__(64 * PHMRF_STRIP_WPB, PHMRF_STRIP_WPE) void strip_k
                                                     unsigned long long* __restrict__ changed, int debug,
                                                     uint16_t* __restrict__ stamp, uint16_t* __restrict__ memo, int tick,
                                                     unsigned long long* __restrict__ work) {
+  // precondition of debug & 4 (launch_strip_pass grants the bit on it): `changed` is counters[COUNTER_EXPANSION + alpha] of a bank
+#define PHMRF_TRACE(which_) (changed - alpha - COUNTER_EXPANSION + COUNTER_TRACE + (which_))      /* that bank's trace counter */
   __shared__ __attribute__((aligned(16))) float tabs[PHMRF_STRIP_WPB * SLAB];   // one 9.1 KB slab per wave: phase-1 staging, then the cost tables of the pass walked
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int WPB = blockDim.x >> 6;
@@ -337,7 +339,7 @@ __global__ __launch_bounds__(64 * PHMRF_STRIP_WPB, PHMRF_STRIP_WPE) void strip_k
     // ---- memo test (inside a solve, fixed cuts): a (dilated) change stamp is renewed whenever the node or one of its
     //      neighbours changes label, so the newest stamp among the strip's cells covers the fixed border too.  If nothing
     //      changed since this very strip was last found quiet for this move, its inputs are identical -> nothing to do.
-    if ((debug & 4) && lane == 0) atomicAdd(changed - alpha - 8 + 100, 1ull);   // strips seen (expansion slots only)
+    if ((debug & 4) && lane == 0) atomicAdd(PHMRF_TRACE(TRACE_SEEN), 1ull);
     uint16_t* my_memo = memo ? memo + (int64_t)strip * (K + 1) + (alpha >= 0 ? alpha : K) : nullptr;
     if (my_memo) {
       const int last_quiet = *my_memo;
@@ -489,7 +491,7 @@ __global__ __launch_bounds__(64 * PHMRF_STRIP_WPB, PHMRF_STRIP_WPE) void strip_k
         }
       }
     }
-    if ((debug & 4) && lane == 0) atomicAdd(changed - alpha - 8 + 101, 1ull);   // strips reaching phase 1
+    if ((debug & 4) && lane == 0) atomicAdd(PHMRF_TRACE(TRACE_PAST_MEMO), 1ull);   // strips reaching phase 1
     if (lane == 0) {
       atomicAdd(&wk[0], 1u);
       atomicAdd(&wk[1], (unsigned int)ncell);                  // nodes this unit re-decides
@@ -645,8 +647,8 @@ __global__ __launch_bounds__(64 * PHMRF_STRIP_WPB, PHMRF_STRIP_WPE) void strip_k
 
     if (lane == 0) atomicAdd(&wk[3], (unsigned int)(t_end - t_lo + 1));
     if ((debug & 4) && lane == 0) {
-      atomicAdd(changed - alpha - 8 + 102, 1ull);                                // strips reaching the DP
-      atomicAdd(changed - alpha - 8 + 103, (unsigned long long)(t_end - t_lo + 1));   // DP steps
+      atomicAdd(PHMRF_TRACE(TRACE_INTO_DP), 1ull);
+      atomicAdd(PHMRF_TRACE(TRACE_DP_STEPS), (unsigned long long)(t_end - t_lo + 1));
     }
     // ---- phase 2: lane <-> state.  Records are broadcast with v_readlane, decisions are one 64-bit ballot per step
     //      parked in lane (t mod 64) of a per-pass register pair.
@@ -672,7 +674,8 @@ __global__ __launch_bounds__(64 * PHMRF_STRIP_WPB, PHMRF_STRIP_WPE) void strip_k
       if (my_memo && lane == 0) *my_memo = (uint16_t)tick;
       continue;
     }
-    if ((debug & 4) && lane == 0) atomicAdd(changed - alpha - 8 + 104, 1ull);   // DPs that found a move
+    if ((debug & 4) && lane == 0) atomicAdd(PHMRF_TRACE(TRACE_MOVED), 1ull);
+#undef PHMRF_TRACE
     // a move exists (about 3 strips in 1000): walk the DP again, this time recording the decision ballots
     m = lane == 0 ? 0.f : BIG;
     dp_pass<0, true>(m, took, lane, tab, rc0[0], rc1[0], rwu[0], rwlu[0], rwl[0], rwld[0], rbits[0], t_lo, t_end, dlo[0], dhi[0]);
@@ -991,11 +994,20 @@ __device__ __forceinline__ void slab_record(const float* slabw, const unsigned c
 #ifndef PHMRF_DP_INLINE
 #define PHMRF_DP_INLINE __noinline__
 #endif
+// -DPHMRF_DP_COUNT (a hand-set development switch, no build of the Makefile): strip_cols_kernel, fusion_cols_kernel and their
+// DP take one more argument, the address of the bank's counters[COUNTER_TRACE], and count into it (PHMRF_SOLVE_TRACE prints them)
+#ifdef PHMRF_DP_COUNT
+#define PHMRF_DP_TRACE_PARAM , unsigned long long* trace
+#define PHMRF_DP_TRACE_ARG(p_) , (p_)
+#else
+#define PHMRF_DP_TRACE_PARAM
+#define PHMRF_DP_TRACE_ARG(p_)
+#endif
 template <int ORIENT, bool FUSION>
 __device__ PHMRF_DP_INLINE unsigned int dp_flagged(StripGeom g, unsigned int lds, int kb, int lane,
                                                    int rs0, int ca, int ncols, int ncell, int alpha, int tick_a, int64_t n, int D,
                                                    const int32_t* nbr_, const float* uT_, uint8_t* labels_, uint16_t* stamp_,
-                                                   uint16_t* mslot_, unsigned long long* changed_slot) {
+                                                   uint16_t* mslot_, unsigned long long* changed_slot PHMRF_DP_TRACE_PARAM) {
     const global_ptr<const int32_t> nbr = as_global(nbr_);
     const global_ptr<const float> uT = as_global(uT_);
     const global_ptr<uint8_t> labels = as_global(labels_);
@@ -1052,9 +1064,9 @@ __device__ PHMRF_DP_INLINE unsigned int dp_flagged(StripGeom g, unsigned int lds
 #endif
 #ifdef PHMRF_DP_COUNT
     if (lane == 0) {                     // development build: solver-trace counters (PHMRF_SOLVE_TRACE)
-      atomicAdd(changed_slot - (FUSION ? 0 : alpha) - 8 + 100, 1ull);
-      atomicAdd(changed_slot - (FUSION ? 0 : alpha) - 8 + 102, 1ull);
-      atomicAdd(changed_slot - (FUSION ? 0 : alpha) - 8 + 103, (unsigned long long)(t_end - t_lo + 1));
+      atomicAdd(trace + TRACE_SEEN, 1ull);
+      atomicAdd(trace + TRACE_INTO_DP, 1ull);
+      atomicAdd(trace + TRACE_DP_STEPS, (unsigned long long)(t_end - t_lo + 1));
     }
 #endif
     // which table chunks hold, or directly follow, a cell of U (see dp_chunk)
@@ -1115,7 +1127,7 @@ __device__ PHMRF_DP_INLINE unsigned int dp_flagged(StripGeom g, unsigned int lds
       return 0u;
     }
 #ifdef PHMRF_DP_COUNT
-    if (lane == 0) atomicAdd(changed_slot - (FUSION ? 0 : alpha) - 8 + 104, 1ull);
+    if (lane == 0) atomicAdd(trace + TRACE_MOVED, 1ull);
 #endif
     DPH(4)
     // a move exists: walk again, this time recording the decision ballots
@@ -1502,7 +1514,7 @@ __global__ __launch_bounds__(64, PHMRF_COLS_WPE) void strip_cols_kernel(StripGeo
                                                                          float beta, unsigned long long label_mask,
                                                                          unsigned long long* __restrict__ changed,
                                                                          uint16_t* __restrict__ stamp, uint16_t* __restrict__ memo,
-                                                                         int tick0, unsigned long long* __restrict__ work, int peel_max) {
+                                                                         int tick0, unsigned long long* __restrict__ work, int peel_max PHMRF_DP_TRACE_PARAM) {
   __shared__ ColsLds lds_pool;
   float* slabw = lds_pool.slabw;
   unsigned char* slabl = lds_pool.slabl;
@@ -1666,7 +1678,7 @@ __global__ __launch_bounds__(64, PHMRF_COLS_WPE) void strip_cols_kernel(StripGeo
       for (int kb = 0; kb < nbuf; ++kb) {
         const int alpha = __builtin_amdgcn_readfirstlane(abuf[kb]);
         const unsigned int my_changed = dp_flagged<ORIENT, false>(g, lds, kb, lane, rs0, ca, ncols, ncell, alpha, tick0 + alpha, n, D, nbr,
-                                                                  uT, labels, stamp, mrow ? mrow + alpha : nullptr, changed + alpha);
+                                                                  uT, labels, stamp, mrow ? mrow + alpha : nullptr, changed + alpha PHMRF_DP_TRACE_ARG(trace));
         PH(4)
         if (my_changed) {
           // the labels of this strip have changed: everything later is filtered again on the new labelling (the slab's
@@ -1725,7 +1737,7 @@ __global__ __launch_bounds__(64, PHMRF_FUSION_WPE) void fusion_cols_kernel(Strip
                                                                           const float* __restrict__ sgain, float beta,
                                                                           unsigned long long* __restrict__ changed,
                                                                           uint16_t* __restrict__ stamp, uint16_t* __restrict__ memo,
-                                                                          int tick, unsigned long long* __restrict__ work, int peel_max) {
+                                                                          int tick, unsigned long long* __restrict__ work, int peel_max PHMRF_DP_TRACE_PARAM) {
   __shared__ FusLds lds_pool;
   float* slabw = lds_pool.c.slabw;
   unsigned char* slabl = lds_pool.c.slabl;
@@ -1913,7 +1925,7 @@ __global__ __launch_bounds__(64, PHMRF_FUSION_WPE) void fusion_cols_kernel(Strip
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    dp_flagged<ORIENT, true>(g, lds, 0, lane, rs0, ca, ncols, ncell, -1, tick, n, D, nbr, uT, labels, stamp, mslot, changed);
+    dp_flagged<ORIENT, true>(g, lds, 0, lane, rs0, ca, ncols, ncell, -1, tick, n, D, nbr, uT, labels, stamp, mslot, changed PHMRF_DP_TRACE_ARG(trace));
     __builtin_amdgcn_wave_barrier();
   }
   __syncthreads();
@@ -2068,7 +2080,7 @@ inline int vec_of(int K) { return (K % 4 == 0) ? 4 : (K % 2 == 0 ? 2 : 1); }
 // Development knobs (read from the environment) exist only in builds with -DPHMRF_DEV (tools/variant.sh): the product
 // library has none that can change or break a labelling.
 #ifdef PHMRF_DEV
-static int strip_debug() {   // timing experiments only (PHMRF_STRIP_DEBUG=1: phase 1 only, 2: no backtrack/apply, +4: count strips)
+static int strip_debug() {   // timing experiments only (PHMRF_STRIP_DEBUG=1: phase 1 only, 2: no backtrack/apply, +4: count strips into the trace counters)
   static int v = -1;
   if (v < 0) {
     const char* e = PHMRF_DEV_ENV("PHMRF_STRIP_DEBUG");
@@ -2173,7 +2185,7 @@ int launch_strip_pass(const phmrf_block* b, float beta, int orient, int shift_r,
 #define PHMRF_LAUNCH_FUSION(O_)                                                                                       \
   hipLaunchKernelGGL((fusion_cols_kernel<O_>), dim3(fgrid), dim3(64), 0, b->stream, g, b->n, b->K, b->D, b->nbr, b->fwd_w,  \
                      b->uT, b->labels, b->labels_tmp, b->sgain, beta, b->counters + b->counter_slot,                   \
-                     b->tick ? b->stamp : nullptr, fmemo, b->tick, b->work_acc, peel_sweeps())
+                     b->tick ? b->stamp : nullptr, fmemo, b->tick, b->work_acc, peel_sweeps() PHMRF_DP_TRACE_ARG(b->counters + COUNTER_TRACE))
     if (orient) PHMRF_LAUNCH_FUSION(1);
     else PHMRF_LAUNCH_FUSION(0);
 #undef PHMRF_LAUNCH_FUSION
@@ -2186,12 +2198,16 @@ int launch_strip_pass(const phmrf_block* b, float beta, int orient, int shift_r,
 #else
   constexpr bool no_pin_look = false, child_count = false;
 #endif
-  const int pin_look = b->unary_pins ? ((no_pin_look ? 0 : 32) | (child_count ? 4 : 0)) : 0;   // (coarse child problems)
+  const int pin_look = (b->unary_pins && !no_pin_look) ? 32 : 0;       // (coarse child problems)
+  // strip_kernel finds the bank's trace counters from the counter it is given (its precondition): only a launch that counts
+  // into the slot of its label's expansions is granted the trace bit -- a coarse child's passes are, into the child's bank
+  const bool can_trace = alpha >= 0 && b->counter_slot == COUNTER_EXPANSION + alpha;
+  const int knobs = strip_debug() | ((b->unary_pins && child_count) ? 4 : 0);
+  const int debug = (can_trace ? knobs : (knobs & 3)) | pin_look;
 #define PHMRF_LAUNCH_STRIP(O_)                                                                                        \
   hipLaunchKernelGGL((strip_kernel<O_>), dim3(grid), dim3(TB), 0, b->stream, g, b->n, b->K, b->D, b->nbr, b->fwd_w, b->uT, \
                      b->labels, alpha < 0 ? b->labels_tmp : nullptr, alpha, beta, b->counters + b->counter_slot,       \
-                     ((alpha >= 0 && b->counter_slot == 8 + alpha) ? strip_debug() : (strip_debug() & 3)) | pin_look,  \
-                     b->tick ? b->stamp : nullptr,                                                                     \
+                     debug, b->tick ? b->stamp : nullptr,                                                              \
                      use_memo ? b->memo + ((int64_t)(orient * 3 + geom) * b->memo_strips) * (b->K + 1) : nullptr,      \
                      b->tick, b->work_acc)
   if (orient) PHMRF_LAUNCH_STRIP(1);
@@ -2221,8 +2237,8 @@ int launch_strip_multi(const phmrf_block* b, float beta, int orient, int shift_r
   uint16_t* const mmemo = use_memo ? b->memo + ((int64_t)(orient * 3 + geom) * b->memo_strips) * (b->K + 1) : nullptr;
 #define PHMRF_LAUNCH_MULTI(O_)                                                                                        \
   hipLaunchKernelGGL((strip_cols_kernel<O_>), dim3(grid), dim3(TB), 0, b->stream, g, b->n, b->K, b->D, b->nbr, b->fwd_w, \
-                     b->uT, b->labels, beta, label_mask, b->counters + 8, b->tick ? b->stamp : nullptr, mmemo,          \
-                     b->tick, b->work_acc, peel_sweeps())
+                     b->uT, b->labels, beta, label_mask, b->counters + COUNTER_EXPANSION, b->tick ? b->stamp : nullptr, \
+                     mmemo, b->tick, b->work_acc, peel_sweeps() PHMRF_DP_TRACE_ARG(b->counters + COUNTER_TRACE))
   if (orient) PHMRF_LAUNCH_MULTI(1);
   else PHMRF_LAUNCH_MULTI(0);
 #undef PHMRF_LAUNCH_MULTI

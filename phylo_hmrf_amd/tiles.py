@@ -19,6 +19,8 @@ import math
 
 import numpy as np
 
+from ._lib import N_COUNTERS
+
 
 # ---- geometry ---------------------------------------------------------------------------------------------------------
 def row_first(i, W, diag):
@@ -158,9 +160,6 @@ class Tile(object):
 
 
 # ---- the tiles of one block ---------------------------------------------------------------------------------------------
-N_COUNTERS = 128
-
-
 class TileGroup(object):
     """The tiles of ONE block: those this rank holds (`local`: {tile index: Tile}) and the transport to the ranks that hold
     the others.  `comm.allreduce_i64(np.int64 array) -> summed array` (identity when every tile is local)."""
@@ -185,7 +184,7 @@ class TileGroup(object):
         for k in self.clock:
             self.clock[k] = 0 if k == "rounds" else 0.0
 
-    # the payload of tile t: [counters 128 | energy 2 (float64 bits) | 1 + the status its holder decided last round |
+    # the payload of tile t: [counters N_COUNTERS | energy 2 (float64 bits) | 1 + the status its holder decided last round |
     # first owned row | last owned row], int64 words
     def _pack(self, buf, t, counters, energy, top, bot):
         o = t * self.slot

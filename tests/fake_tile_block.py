@@ -8,6 +8,7 @@ import numpy as np
 from oracle import mrf_moves as M
 from oracle import ref_numpy as R
 from phylo_hmrf_amd import tiles
+from phylo_hmrf_amd._lib import COUNTER_ICM, N_COUNTERS
 
 PIN = 1.0e9
 
@@ -94,8 +95,8 @@ class FakeTileBlock(object):
         self._changed = int(np.sum(self.labels != before))
 
     def solve_round_collect(self):
-        c = np.zeros(128, dtype=np.uint64)
-        c[76] = self._changed
+        c = np.zeros(N_COUNTERS, dtype=np.uint64)
+        c[COUNTER_ICM] = self._changed
         return c, np.array(self._energy_owned())
 
     def tile_get_boundary(self, top_len, bottom_len):
@@ -115,7 +116,7 @@ class FakeTileBlock(object):
         self.rounds += 1
         self.last_energy = float(energy[0] + self.beta * energy[1])
         # two quiet rounds in a row (one of each pin parity) end the solve; 40 rounds at most
-        quiet = int(counters[76]) == 0
+        quiet = int(counters[COUNTER_ICM]) == 0
         done = quiet and getattr(self, "_prev_quiet", False)
         self._prev_quiet = quiet
         self.status = 1 if done else (2 if self.rounds >= 40 else 0)

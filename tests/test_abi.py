@@ -23,6 +23,19 @@ def test_header_declares_the_hot_path_entry_points():
         assert must in syms
 
 
+def test_python_counter_slots_equal_the_header():
+    """The counter bank of a solve's round crosses the ABI as bare uint64[PHMRF_NUM_COUNTERS]: the Python side's slot names
+    (phylo_hmrf_amd/_lib.py) are the header's macros, every one of them."""
+    from phylo_hmrf_amd import _lib, tiles
+    macros = dict((k, int(v)) for k, v in re.findall(r"^#define\s+PHMRF_(NUM_COUNTERS|COUNTER_\w+)\s+(\d+)\s*$", open(HEADER).read(), re.M))
+    assert sorted(macros) == ["COUNTER_CHAIN", "COUNTER_COARSE", "COUNTER_COMPONENT", "COUNTER_EXPANSION", "COUNTER_FUSION",
+                              "COUNTER_ICM", "NUM_COUNTERS"]
+    assert _lib.N_COUNTERS == tiles.N_COUNTERS == macros.pop("NUM_COUNTERS") == 128
+    for name, value in macros.items():
+        assert getattr(_lib, name) == value, name
+    assert sorted(n for n in dir(_lib) if n.startswith("COUNTER_")) == sorted(macros)
+
+
 @pytest.mark.skipif(not os.path.exists(LIB), reason="libphmrf.so not built (run __graft_entry__.build())")
 def test_library_exports_every_declared_symbol():
     L = ctypes.CDLL(LIB)

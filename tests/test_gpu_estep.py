@@ -919,7 +919,7 @@ def test_deterministic_mode_gives_identical_labellings():
 
 def test_coarse_labels_in_batches_give_the_one_by_one_sequence():
     """The coarse alpha-expansions build four labels' child problems per pass and rebuild a label's problem only after a move
-    (decided on the device, api.hip coarse_sweep_nocount).  The labellings must be those of the one-label-at-a-time order
+    (decided on the device, solve.hip coarse_sweep_nocount).  The labellings must be those of the one-label-at-a-time order
     (PHMRF_COARSE_BATCH=1): with PHMRF_DETERMINISTIC=1 both runs of the cold-start script give the same label hash, round
     count and energy, bit for bit."""
     import subprocess

@@ -128,8 +128,8 @@ def main():
                 owners = sorted(set(int(owner[i]) for i, _ in mine))
                 say("new_group for block %d of %s: ranks %s (%d tiles)" % (bi, wl, owners, len(mine)))
                 grp = dist.new_group(ranks=owners) if len(owners) > 1 else None       # collective: EVERY rank, block order
-                # a lockstep round's payload: per tile 128 counters + (unary, pair) energy + viol + the two boundary rows
-                per_tile = 128 + 3 + 2 * ((W + 7) // 8)
+                # a lockstep round's payload: per tile N_COUNTERS counters + (unary, pair) energy + viol + the two boundary rows
+                per_tile = tiles.N_COUNTERS + 3 + 2 * ((W + 7) // 8)
                 nel = per_tile * len(mine)
                 groups.append((bi, owners, len(mine), nel))
                 if grp is not None:
