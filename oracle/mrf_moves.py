@@ -11,6 +11,11 @@ energy-non-increasing moves that parallelise over nodes / chains:
 This module is the move-by-move model the HIP kernels are tested against (same tie-breaking:
 lowest label wins, a chain keeps its incoming label on ties) and the CPU prototype used to
 choose the move schedule against the gco oracle.  Energies follow SURVEY.md 8(a-E).
+
+Tie rule of the chain move: a chain (segment) whose current labelling already attains the minimum keeps it -- the move
+writes only a STRICTLY lower labelling.  Among strictly better optima the Viterbi ties decide as above.  Without the rule
+the four chain families hand a labelling of exactly equal energy back and forth for ever, and a solve that stops on "the
+energy did not go down" ends with labels still moving: `converged` would not be a fixed point of the chain moves.
 """
 import numpy as np
 
@@ -143,8 +148,8 @@ def link_weights(g, nodes):
 
 
 def chain_move(g, unary, labels, beta, nodes, lens, sel):
-    """Exact re-labelling of the selected chains (rows of `nodes` where sel), in place.
-    Returns the number of nodes whose label changed."""
+    """Exact re-labelling of the selected chains (rows of `nodes` where sel), in place.  A chain whose labelling already
+    attains the minimum keeps it (the module's tie rule).  Returns the number of nodes whose label changed."""
     K = unary.shape[1]
     nd = nodes[sel]
     ln = lens[sel]
@@ -165,7 +170,13 @@ def chain_move(g, unary, labels, beta, nodes, lens, sel):
     m = theta[:, 0, :].copy()
     jump = np.zeros((C, L, K), dtype=bool)                 # True: best predecessor is the global argmin
     amin = np.zeros((C, L), dtype=np.int64)
+    old = labels[safe]
+    rows = np.arange(C)
+    cur_cost = theta[rows, 0, old[:, 0]].copy()            # the current labelling's cost, summed in the DP's own order
     for t in range(1, L):
+        live = valid[:, t]
+        step = theta[rows, t, old[:, t]] + np.where(old[:, t] != old[:, t - 1], cur_cost + lw[:, t - 1], cur_cost)
+        cur_cost = np.where(live, step, cur_cost)
         mm = m.min(axis=1)
         am = m.argmin(axis=1)
         alt = mm + lw[:, t - 1]
@@ -184,7 +195,7 @@ def chain_move(g, unary, labels, beta, nodes, lens, sel):
         if t > 0:
             jp = jump[np.arange(C), t, cur]
             cur = np.where(live & jp, amin[:, t], cur)
-    old = labels[safe]
+    new = np.where((m.min(axis=1) < cur_cost)[:, None], new, old)      # only a strictly lower labelling is written
     ch = int(np.sum((new != old) & valid))
     labels[nd[valid]] = new[valid]
     return ch
@@ -312,9 +323,19 @@ def strip_node_table(H, W, diagonal, orient, shift_r, shift_c):
 
 def strip_fusion(g, unary, labels, prop, beta, H, W, diagonal, orient, shift_r, shift_c):
     """Exact binary fusion x_i in {keep l_i, take prop_i} over every strip simultaneously (profile DP over
-    2^(STRIP_H+1) states).  In place; returns the number of changed nodes."""
+    2^(STRIP_H+1) states).  In place; returns the number of changed nodes.
+
+    Tie rule (the kernels', strip.hip): the DP walks on past a strip's last cell through STRIP_H + 1 cells that can only
+    keep, so it always ends in the all-keep profile, and the backtrack decides every cell by the step rule below ("ties keep
+    the predecessor whose leaving bit equals the new cell's bit").  Among labellings of exactly equal energy this prefers
+    "keep" for the LAST cell first, then for the one before it, and so on; all-keep wins whenever it is optimal.  (Taking
+    the lowest profile index at the strip's own last cell instead prefers "keep" for the oldest cell of the profile first:
+    the same energy, another labelling.)"""
     h = STRIP_H
     nodes, ncols = strip_node_table(H, W, diagonal, orient, shift_r, shift_c)
+    if nodes.size == 0:
+        return 0
+    nodes = np.concatenate([nodes, -np.ones((nodes.shape[0], h + 1), dtype=np.int64)], axis=1)     # the keep-only cells
     NS, T = nodes.shape
     n = g.n
     valid = nodes >= 0
@@ -360,8 +381,6 @@ def strip_fusion(g, unary, labels, prop, beta, H, W, diagonal, orient, shift_r, 
     bbit = st & 1
     m = np.zeros((NS, NSt))
     back = np.zeros((NS, T, NSt), dtype=bool)
-    ncell = ncols * h
-    s_fin = np.zeros(NS, dtype=np.int64)
     for t in range(T):
         def total(pred):
             cost = np.where(bbit[None, :] == 1, C1[:, t][:, None], C0[:, t][:, None])
@@ -379,15 +398,12 @@ def strip_fusion(g, unary, labels, prop, beta, H, W, diagonal, orient, shift_r, 
         take1 = np.where(bbit[None, :] == 1, a1 <= a0, a1 < a0)
         m = np.where(take1, a1, a0)
         back[:, t, :] = take1
-        done = ncell == t + 1
-        s_fin[done] = np.argmin(m[done], axis=1)       # the kernel stops at the strip's own last cell
-    s = s_fin.copy()
+    s = np.zeros(NS, dtype=np.int64)                   # (every cell of the last profile is a keep-only cell)
     x = np.zeros((NS, T), dtype=np.int64)
     for t in range(T - 1, -1, -1):
-        live = t < ncell
-        x[:, t] = np.where(live, s & 1, 0)
+        x[:, t] = s & 1
         d = back[np.arange(NS), t, s]
-        s = np.where(live, (s >> 1) | (d.astype(np.int64) << h), s)
+        s = (s >> 1) | (d.astype(np.int64) << h)
     newlab = np.where(x == 1, prv, labv)
     ch = int(((newlab != labv) & valid).sum())
     labels[nodes[valid]] = newlab[valid]

@@ -266,6 +266,13 @@ namespace phmrf {
 #else
 #define PHMRF_DEV_ENV(name) (static_cast<const char*>(nullptr))
 #endif
+// development: A/B of the exact skips.  With PHMRF_NO_SKIP the strip and chain launches of a solve pass no memo of quiet
+// runs and launch_propose recomputes every proposal; the stamps are still written and nothing else changes, so a solve must
+// walk through the same labellings with and without it (tests/test_gpu_exact_skips.py).
+inline bool no_skip() {
+  static const bool v = PHMRF_DEV_ENV("PHMRF_NO_SKIP") != nullptr;
+  return v;
+}
 constexpr int C2F_SCALE = 4;          // super-cells of the coarse-to-fine start (c2f.hip)
 constexpr int UT_PAD = 64;            // floats of slack before and after the unary planes (strip.hip: launch_unary_planes)
 constexpr int WORK_SLOTS = 7;         // see phmrf_block_get_work (phmrf_block_get_work_ex's entries 8, 9 have no device slot)

@@ -7,6 +7,11 @@
 //                    like the ICM tile), phase 2 maps lane <-> label: the min over labels is a DPP wave
 //                    reduction, argmin / jump decisions are 64-bit ballots kept one step per lane
 //                    (one v_cndmask per value), and the backtrack runs on scalars (v_readlane).
+//                    Tie rule: a segment whose labelling already attains the minimum keeps it -- only a STRICTLY lower
+//                    labelling is written (the cost of the current labelling is carried through the forward pass in
+//                    the DP's own order of additions, so it is never below the minimum the DP finds).  Otherwise the
+//                    families hand labellings of exactly equal energy back and forth, and a solve that ends on "the
+//                    energy did not go down" is no fixed point of the chain moves.
 //  component pass    connected components of equal label (one-pass union-find with atomicCAS hooks), then for
 //                    every component C and label k the exact energy change of relabelling all of C to k,
 //                      dE = sum_{i in C} (u_i(k) - u_i(cur)) - beta * sum_{boundary edges to label k} w,
@@ -135,6 +140,11 @@ __global__ __launch_bounds__(256) void chain_kernel(const float* __restrict__ lo
     const int len2 = (debug == 1 || debug == 3 || debug == 4) ? 0 : len;
     float m = (lane < K && len > 0) ? tile[lane] : BIG;
     unsigned int jm_lo = 0, jm_hi = 0, am_v = 0;  // lane t holds the decisions of step t
+    // the current labelling's own cost (lane <-> node: theta of my label; bit t: my label differs from my predecessor's)
+    const float own = lane < len ? tile[lane * Kp + old] : 0.f;
+    const int old_pv = __shfl_up(old, 1, 64);
+    const unsigned long long differs = __ballot(lane > 0 && lane < len && old != old_pv);
+    float cur_cost = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, own)));
     for (int t = 1; t < len2; ++t) {
       const float th = lane < K ? tile[t * Kp + lane] : 0.f;
       const float mmin = wave_min_f32(m);
@@ -142,6 +152,8 @@ __global__ __launch_bounds__(256) void chain_kernel(const float* __restrict__ lo
       const int am = __ffsll((long long)eq) - 1;
       const float lk = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, link), t - 1));
       const float alt = mmin + beta * lk;
+      const float own_t = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, own), t));
+      cur_cost = own_t + (((differs >> t) & 1ull) ? cur_cost + beta * lk : cur_cost);
       const bool jp = (lane < K) && (alt < m);
       const unsigned long long jm = __ballot(jp);
       m = lane < K ? th + (jp ? alt : m) : BIG;
@@ -155,14 +167,16 @@ __global__ __launch_bounds__(256) void chain_kernel(const float* __restrict__ lo
     int newl = old;
     if (len2 > 0 && debug != 2) {
       const float mmin = wave_min_f32(m);
-      int cur = __ffsll((long long)__ballot(m == mmin)) - 1;
-      for (int t = len - 1; t >= 1; --t) {
-        if (lane == t) newl = cur;
-        const unsigned long long jm = ((unsigned long long)__builtin_amdgcn_readlane(jm_hi, t) << 32) |
-                                      (unsigned long long)__builtin_amdgcn_readlane(jm_lo, t);
-        if ((jm >> cur) & 1ull) cur = (int)__builtin_amdgcn_readlane(am_v, t);
+      if (mmin < cur_cost) {              // (the tie rule: only a strictly lower labelling is written)
+        int cur = __ffsll((long long)__ballot(m == mmin)) - 1;
+        for (int t = len - 1; t >= 1; --t) {
+          if (lane == t) newl = cur;
+          const unsigned long long jm = ((unsigned long long)__builtin_amdgcn_readlane(jm_hi, t) << 32) |
+                                        (unsigned long long)__builtin_amdgcn_readlane(jm_lo, t);
+          if ((jm >> cur) & 1ull) cur = (int)__builtin_amdgcn_readlane(am_v, t);
+        }
+        if (lane == 0) newl = cur;
       }
-      if (lane == 0) newl = cur;
     }
     const bool seg_changed = __any(lane < len && newl != old);
     if (memo && ran && lane == 0) memo[seg] = seg_changed ? (uint16_t)0 : (uint16_t)tick;
@@ -745,7 +759,7 @@ int launch_chain_colour(const phmrf_block* b, float beta, int family, int colour
   hipLaunchKernelGGL((chain_kernel<VEC_>), dim3(grid), dim3(TB), lds, b->stream, b->logprob, f.nodes,                  \
                      f.seg_start[phase][colour], f.seg_len[phase][colour], nseg, K, Kp, b->D, b->nbr, b->wgt, b->labels, \
                      beta, b->counters + b->counter_slot, chain_debug(), b->tick ? b->stamp : nullptr, b->tick, \
-                     (b->tick && f.memo[phase][colour]) ? f.memo[phase][colour] : nullptr)
+                     (b->tick && f.memo[phase][colour] && !no_skip()) ? f.memo[phase][colour] : nullptr)
   switch (vec_of(K)) {
     case 4: PHMRF_LAUNCH_CHAIN(4); break;
     case 2: PHMRF_LAUNCH_CHAIN(2); break;

@@ -2104,7 +2104,7 @@ static constexpr int peel_sweeps() { return PEEL_MAX; }
 #endif
 
 int launch_propose(phmrf_block* b, float beta) {
-  const int since = b->tick ? b->prop_tick : -1;
+  const int since = (b->tick && !no_skip()) ? b->prop_tick : -1;
   if (!b->sgain) PHMRF_HIP(hipMalloc(reinterpret_cast<void**>(&b->sgain), (size_t)b->n * sizeof(float)));
   const int K = b->K, TB = tile_threads(K), Kp = padded_k(K);
   const size_t lds = (size_t)TB * Kp * sizeof(float);
@@ -2175,7 +2175,7 @@ int launch_strip_pass(const phmrf_block* b, float beta, int orient, int shift_r,
   const int WPB = PHMRF_STRIP_WPB, TB = 64 * WPB;
   int grid = (nstrips + WPB - 1) / WPB;
   if (grid > (1 << 22)) grid = 1 << 22;          // one workgroup per strip (see launch_strip_multi)
-  const bool use_memo = b->tick && geom >= 0 && b->memo && (int64_t)nstrips <= b->memo_strips;
+  const bool use_memo = b->tick && geom >= 0 && b->memo && (int64_t)nstrips <= b->memo_strips && !no_skip();
   // the fusion pass of a solve (proposals in labels_tmp) runs behind the exact filter (fusion_cols_kernel); the
   // single-label passes of the API and the coarse child problems keep strip_kernel.
   if (alpha < 0) {
@@ -2233,7 +2233,7 @@ int launch_strip_multi(const phmrf_block* b, float beta, int orient, int shift_r
   // of 8 resident sets: -3 % on the rows cut)
   int grid = strip_slots(orient, g.nbands, g.nsegs, g.xcd);
   if (grid > (1 << 22)) grid = 1 << 22;
-  const bool use_memo = b->tick && geom >= 0 && b->memo && (int64_t)nstrips <= b->memo_strips;
+  const bool use_memo = b->tick && geom >= 0 && b->memo && (int64_t)nstrips <= b->memo_strips && !no_skip();
   uint16_t* const mmemo = use_memo ? b->memo + ((int64_t)(orient * 3 + geom) * b->memo_strips) * (b->K + 1) : nullptr;
 #define PHMRF_LAUNCH_MULTI(O_)                                                                                        \
   hipLaunchKernelGGL((strip_cols_kernel<O_>), dim3(grid), dim3(TB), 0, b->stream, g, b->n, b->K, b->D, b->nbr, b->fwd_w, \

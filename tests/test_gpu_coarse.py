@@ -6,7 +6,7 @@ import pytest
 from oracle import mrf_moves as M
 from oracle import ref_numpy as R
 from oracle import synth
-from tests.test_gpu_estep import _block, _integer_problem
+from tests.test_gpu_estep import _as_before, _block, _integer_problem
 
 pytestmark = pytest.mark.gpu
 
@@ -35,8 +35,9 @@ def test_coarse_problem_matches_model(H, W, K, diagonal, scale):
     b.close()
 
 
-@pytest.mark.parametrize("H,W,K,diagonal", [(60, 60, 5, True), (33, 90, 4, False), (150, 150, 8, True)])
-def test_coarse_pass_matches_move_model(H, W, K, diagonal):
+@pytest.mark.parametrize("H,W,K,diagonal,beta", [_as_before(60, 60, 5, True, 1.0), _as_before(33, 90, 4, False, 1.0),
+                                                 _as_before(150, 150, 8, True, 1.0), (60, 60, 5, True, 0.5), (33, 90, 4, False, 2.0)])
+def test_coarse_pass_matches_move_model(H, W, K, diagonal, beta):
     n, eid, w, lp, init = _integer_problem(21, H, W, K, diagonal)
     g = M.Graph(n, eid, w)
     b = _block(n, 2, K)
@@ -47,11 +48,11 @@ def test_coarse_pass_matches_move_model(H, W, K, diagonal):
     lab = init.astype(np.int64).copy()
     for it, (scale, off, alpha, sr, sc) in enumerate([(2, 0, 1, 0, 0), (4, 3, 0, 2, 40), (2, 1, 2, 5, 63), (4, 0, 3, 1, 7),
                                                        (2, 0, 0, 3, 21)]):
-        e0 = M.energy(g, -lp, lab, 1.0)[0]
-        ch_ref = M.coarse_expansion(g, -lp, lab, 1.0, H, W, diagonal, scale, off, alpha, sr, sc)
-        ch = b.coarse_pass(1.0, scale, off, alpha, sr, sc)
+        e0 = M.energy(g, -lp, lab, beta)[0]
+        ch_ref = M.coarse_expansion(g, -lp, lab, beta, H, W, diagonal, scale, off, alpha, sr, sc)
+        ch = b.coarse_pass(beta, scale, off, alpha, sr, sc)
         got = b.get_labels().astype(np.int64)
-        assert M.energy(g, -lp, lab, 1.0)[0] <= e0 + 1e-9
+        assert M.energy(g, -lp, lab, beta)[0] <= e0 + 1e-9
         assert np.array_equal(got, lab), (it, int((got != lab).sum()))
         assert ch == ch_ref
     b.close()

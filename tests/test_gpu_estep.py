@@ -16,6 +16,7 @@ import pytest
 from oracle import mrf_moves as M
 from oracle import ref_numpy as R
 from oracle import synth
+from tests.fixed_point_audit import segment_chain_model as _segment_chain_model
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -90,7 +91,9 @@ def test_emission_ou_params_golden_chain():
 # ------------------------------------------------------------------------------------------------ b2
 def _integer_problem(seed, H, W, K, diagonal):
     """Unaries and weights are small integers / dyadic rationals: f32 arithmetic is exact, so the GPU moves must
-    reproduce the float64 move model label for label."""
+    reproduce the float64 move model label for label.  Unaries are multiples of 0.5 and weights multiples of 1/8, so with
+    beta in BETAS every term is a multiple of 1/16; a strip's sums stay below 315 cells x 24 < 2^13 and a whole block's
+    below 2^20 sixteenths: exact in f32 and in the 2^-16 fixed point of the deterministic component table."""
     rng = np.random.default_rng(seed)
     n = H * (H + 1) // 2 if diagonal else H * W
     X = rng.uniform(0.5, 2, (n, 2))
@@ -109,12 +112,47 @@ def _integer_problem(seed, H, W, K, diagonal):
     return n, eid, w, -un, init
 
 
-@pytest.mark.parametrize("H,W,K,diagonal", [(23, 70, 4, False), (41, 41, 6, True), (6, 200, 3, False), (130, 7, 5, False),
-                                            (64, 129, 20, False), (3, 3, 2, True), (30, 66, 64, False), (35, 35, 30, True)])
-def test_strip_multi_pass_matches_the_single_label_passes(H, W, K, diagonal):
+BETAS = (0.5, 1.0, 2.0)
+
+
+def _as_before(*values):
+    """a case that existed before the tests took (seed, beta, cuts, variant): it keeps its id"""
+    return pytest.param(*values, id="-".join(str(v) for v in values[:4]))
+
+
+# Shapes that put a strip's end on the edges of its 63-column window and its 5-row band, and the cuts that go with them
+# (the window's first and last shift, one off either): every shape runs every cut in both orientations.
+EDGE_SHAPES = [(12, 63, False), (12, 64, False), (12, 65, False), (12, 127, False), (12, 128, False), (5, 70, False),
+               (6, 70, False), (7, 70, False), (11, 70, False), (63, 63, True), (64, 64, True), (65, 65, True)]
+EDGE_CUTS = [(0, 0), (5, 63), (1, 1), (4, 62)]
+# (seeds 4, 6, 11 and the three betas dealt over the shapes)
+EDGE_CASES = [(H, W, 3, diag, (4, 6, 11)[i % 3], BETAS[(i // 3 + i) % 3], "edge", "plain") for i, (H, W, diag) in enumerate(EDGE_SHAPES)]
+
+
+def _variant(variant, n, K, w, init):
+    """the degenerate inputs of the strip tests"""
+    if variant == "zero weights":          # every node independent: the per-node argmin, ties to the current label
+        return np.zeros_like(w), init
+    if variant == "constant":              # one label everywhere, label K - 1 absent
+        return w, np.full(n, min(1, K - 2))
+    assert variant == "plain"
+    return w, init
+
+
+MULTI_CASES = [_as_before(H, W, K, d, 6, 1.0, "std", "plain") for H, W, K, d in
+               [(23, 70, 4, False), (41, 41, 6, True), (6, 200, 3, False), (130, 7, 5, False), (64, 129, 20, False),
+                (3, 3, 2, True), (30, 66, 64, False), (35, 35, 30, True)]]
+MULTI_CASES += [(23, 70, 4, False, 4, 0.5, "std", "plain"), (41, 41, 6, True, 11, 2.0, "std", "plain"),
+                (30, 66, 64, False, 4, 0.5, "std", "plain"), (23, 70, 4, False, 6, 2.0, "std", "zero weights"),
+                (41, 41, 6, True, 6, 0.5, "std", "constant")] + EDGE_CASES
+
+
+@pytest.mark.parametrize("H,W,K,diagonal,seed,beta,cuts,variant", MULTI_CASES)
+def test_strip_multi_pass_matches_the_single_label_passes(H, W, K, diagonal, seed, beta, cuts, variant):
     """strip_cols_kernel (every label of a cut in one launch, behind the exact filter) = the strip alpha-expansions of
     the move model applied label after label, label for label -- the filter loses no move and breaks no tie differently."""
-    n, eid, w, lp, init = _integer_problem(6, H, W, K, diagonal)
+    n, eid, w, lp, init = _integer_problem(seed, H, W, K, diagonal)
+    w, init = _variant(variant, n, K, w, init)
     g = M.Graph(n, eid, w)
     b = _block(n, 2, K)
     b.set_graph(eid, w)
@@ -123,22 +161,30 @@ def test_strip_multi_pass_matches_the_single_label_passes(H, W, K, diagonal):
     b.set_labels(init)
     lab = init.astype(np.int64).copy()
     total = 0
-    for it, (orient, sr, sc, labels) in enumerate([(0, 0, 0, None), (1, 3, 17, None), (0, 2, 40, [K - 1, 0]), (1, 5, 63, None),
-                                                   (0, 4, 21, None), (1, 0, 42, None)]):
+    passes = [(0, 0, 0, None), (1, 3, 17, None), (0, 2, 40, [K - 1, 0]), (1, 5, 63, None), (0, 4, 21, None), (1, 0, 42, None)]
+    if cuts == "edge":
+        passes = [(orient, sr, sc, None) for sr, sc in EDGE_CUTS for orient in (0, 1)]
+    for it, (orient, sr, sc, labels) in enumerate(passes):
         ch_ref = 0
         for alpha in (range(K) if labels is None else sorted(labels)):
-            ch_ref += M.strip_fusion(g, -lp, lab, np.full(n, alpha), 1.0, H, W, diagonal, orient, sr, sc)
-        ch = b.strip_multi_pass(1.0, orient, sr, sc, labels)
+            ch_ref += M.strip_fusion(g, -lp, lab, np.full(n, alpha), beta, H, W, diagonal, orient, sr, sc)
+        ch = b.strip_multi_pass(beta, orient, sr, sc, labels)
         got = b.get_labels().astype(np.int64)
         assert np.array_equal(got, lab), (it, int((got != lab).sum()))
         assert ch == ch_ref
         total += ch
     assert total > 0 or n < 20
+    if variant == "zero weights" and cuts == "std":
+        # independent nodes: whatever lay inside a strip of some pass is at its own argmin, or tied with it
+        un = -lp
+        assert np.mean(un[np.arange(n), lab] == un.min(axis=1)) > 0.9
     b.close()
 
 
-@pytest.mark.parametrize("H,W,K,diagonal", [(37, 37, 5, True), (30, 45, 8, False), (70, 70, 20, True), (9, 200, 3, False)])
-def test_icm_sweep_matches_move_model(H, W, K, diagonal):
+@pytest.mark.parametrize("H,W,K,diagonal,beta", [_as_before(37, 37, 5, True, 1.0), _as_before(30, 45, 8, False, 1.0),
+                                                 _as_before(70, 70, 20, True, 1.0), _as_before(9, 200, 3, False, 1.0),
+                                                 (37, 37, 5, True, 0.5), (30, 45, 8, False, 2.0)])
+def test_icm_sweep_matches_move_model(H, W, K, diagonal, beta):
     n, eid, w, lp, init = _integer_problem(1, H, W, K, diagonal)
     g = M.Graph(n, eid, w)
     col, nc = M.icm_colours(H, W, diagonal)
@@ -149,12 +195,12 @@ def test_icm_sweep_matches_move_model(H, W, K, diagonal):
     b.set_labels(init)
     lab = init.astype(np.int64).copy()
     for sweep in range(3):
-        ch_ref = M.icm_sweep(g, -lp, lab, 1.0, col, nc)
-        ch = b.icm_sweep(1.0)
+        ch_ref = M.icm_sweep(g, -lp, lab, beta, col, nc)
+        ch = b.icm_sweep(beta)
         assert ch == ch_ref
         assert np.array_equal(b.get_labels(), lab)
-    e = b.energy(1.0)
-    np.testing.assert_allclose(e[0], M.energy(g, -lp, lab, 1.0)[0], rtol=1e-9)
+    e = b.energy(beta)
+    np.testing.assert_allclose(e[0], M.energy(g, -lp, lab, beta)[0], rtol=1e-9)
     b.close()
 
 
@@ -182,33 +228,14 @@ def test_icm_general_graph_greedy_colouring_never_raises_energy():
     b.close()
 
 
-def _segment_chain_model(g, un, labels, beta, H, W, diagonal, family, phase):
-    """oracle/mrf_moves chain move restricted to the product's segment cut (<=63 nodes, separators fixed)."""
-    fam = M.chain_families(H, W, diagonal, 8)[family]
-    chains, colour, ncol = fam
-    changed = 0
-    for c in range(ncol):
-        segs = []
-        for ch, cc in zip(chains, colour):
-            if cc != c:
-                continue
-            L = len(ch)
-            start, sep = 0, (31 if phase else 63)
-            while start < L:
-                end = min(sep, L)
-                if end > start:
-                    segs.append(ch[start:end])
-                start = sep + 1
-                sep += 64
-        if not segs:
-            continue
-        nodes, lens, col2, _ = M.pack_family((segs, np.zeros(len(segs), dtype=np.int64), 1))
-        changed += M.chain_move(g, un, labels, beta, nodes, lens, np.ones(len(segs), dtype=bool))
-    return changed
-
-
-@pytest.mark.parametrize("H,W,K,diagonal", [(40, 40, 5, True), (33, 150, 8, False), (130, 130, 20, True)])
-def test_chain_sweeps_match_move_model(H, W, K, diagonal):
+@pytest.mark.parametrize("H,W,K,diagonal,beta", [_as_before(40, 40, 5, True, 1.0), _as_before(33, 150, 8, False, 1.0),
+                                                 _as_before(130, 130, 20, True, 1.0), (40, 40, 5, True, 0.5),
+                                                 (33, 150, 8, False, 2.0)])
+def test_chain_sweeps_match_move_model(H, W, K, diagonal, beta):
+    """A family's sweep (two colours, both segment cuts) ends at the model's energy.  The later colours and cuts start
+    from what the earlier ones wrote, so kernel and model must also break exact ties alike: both keep a segment's labelling
+    when it already attains the minimum (oracle/mrf_moves.py, the chain move's tie rule).  A model without that rule parts
+    from the kernel at the first tie and ends the family elsewhere (33 x 150, family 1: 5918.5 against 5921.125)."""
     n, eid, w, lp, init = _integer_problem(2, H, W, K, diagonal)
     g = M.Graph(n, eid, w)
     b = _block(n, 2, K)
@@ -218,21 +245,30 @@ def test_chain_sweeps_match_move_model(H, W, K, diagonal):
     b.set_labels(init)
     lab = init.astype(np.int64).copy()
     for family in range(4):
-        ch_ref = _segment_chain_model(g, -lp, lab, 1.0, H, W, diagonal, family, 0)
-        ch_ref += _segment_chain_model(g, -lp, lab, 1.0, H, W, diagonal, family, 1)
-        ch = b.chain_sweep(1.0, family)
+        ch_ref = _segment_chain_model(g, -lp, lab, beta, H, W, diagonal, family, 0)
+        ch_ref += _segment_chain_model(g, -lp, lab, beta, H, W, diagonal, family, 1)
+        ch = b.chain_sweep(beta, family)
         got = b.get_labels()
-        e_gpu = M.energy(g, -lp, got.astype(np.int64), 1.0)[0]
-        e_ref = M.energy(g, -lp, lab, 1.0)[0]
+        e_gpu = M.energy(g, -lp, got.astype(np.int64), beta)[0]
+        e_ref = M.energy(g, -lp, lab, beta)[0]
         # integer problem: exact arithmetic; ties may be broken differently only if the energies are equal
         assert abs(e_gpu - e_ref) < 1e-9, (family, e_gpu, e_ref)
         lab = got.astype(np.int64).copy()
     b.close()
 
 
-@pytest.mark.parametrize("H,W,K,diagonal", [(23, 70, 4, False), (41, 41, 6, True), (6, 200, 3, False), (130, 7, 5, False)])
-def test_strip_passes_match_move_model(H, W, K, diagonal):
-    n, eid, w, lp, init = _integer_problem(4, H, W, K, diagonal)
+PASS_CASES = [_as_before(H, W, K, d, 4, 1.0, "std", "plain") for H, W, K, d in
+              [(23, 70, 4, False), (41, 41, 6, True), (6, 200, 3, False), (130, 7, 5, False)]]
+# (the fusion pass behind the filter at the two large label counts; the other betas and seeds; the degenerate inputs)
+PASS_CASES += [(64, 129, 20, False, 4, 1.0, "std", "plain"), (30, 66, 64, False, 6, 0.5, "std", "plain"),
+               (23, 70, 4, False, 6, 0.5, "std", "plain"), (41, 41, 6, True, 11, 2.0, "std", "plain"),
+               (23, 70, 4, False, 11, 2.0, "std", "zero weights"), (41, 41, 6, True, 4, 0.5, "std", "constant")] + EDGE_CASES
+
+
+@pytest.mark.parametrize("H,W,K,diagonal,seed,beta,cuts,variant", PASS_CASES)
+def test_strip_passes_match_move_model(H, W, K, diagonal, seed, beta, cuts, variant):
+    n, eid, w, lp, init = _integer_problem(seed, H, W, K, diagonal)
+    w, init = _variant(variant, n, K, w, init)
     g = M.Graph(n, eid, w)
     b = _block(n, 2, K)
     b.set_graph(eid, w)
@@ -240,20 +276,27 @@ def test_strip_passes_match_move_model(H, W, K, diagonal):
     b.set_logprob(lp)
     b.set_labels(init)
     lab = init.astype(np.int64).copy()
-    for it, (orient, sr, sc, alpha) in enumerate([(0, 0, 0, -1), (1, 3, 17, -1), (0, 2, 40, 1), (1, 5, 63, 0), (0, 4, 5, -1)]):
-        prop = M.best_alternative(g, -lp, lab, 1.0) if alpha < 0 else np.full(n, alpha)
-        ch_ref = M.strip_fusion(g, -lp, lab, prop, 1.0, H, W, diagonal, orient, sr, sc)
-        ch = b.strip_pass(1.0, orient, sr, sc, alpha)
+    passes = [(0, 0, 0, -1), (1, 3, 17, -1), (0, 2, 40, 1), (1, 5, 63, 0), (0, 4, 5, -1)]
+    if cuts == "edge":       # every cut in both orientations, the fusion pass and a single label's expansion taking turns
+        passes = [(orient, sr, sc, -1 if (i + orient) % 2 == 0 else (i + orient) % K)
+                  for i, (sr, sc) in enumerate(EDGE_CUTS) for orient in (0, 1)]
+        passes += [(orient, sr, sc, -1 if (i + orient) % 2 else (i + orient) % K)
+                   for i, (sr, sc) in enumerate(EDGE_CUTS) for orient in (0, 1)]
+    for it, (orient, sr, sc, alpha) in enumerate(passes):
+        prop = M.best_alternative(g, -lp, lab, beta) if alpha < 0 else np.full(n, alpha)
+        ch_ref = M.strip_fusion(g, -lp, lab, prop, beta, H, W, diagonal, orient, sr, sc)
+        ch = b.strip_pass(beta, orient, sr, sc, alpha)
         got = b.get_labels().astype(np.int64)
-        e_gpu, e_ref = M.energy(g, -lp, got, 1.0)[0], M.energy(g, -lp, lab, 1.0)[0]
+        e_gpu, e_ref = M.energy(g, -lp, got, beta)[0], M.energy(g, -lp, lab, beta)[0]
         assert abs(e_gpu - e_ref) < 1e-9, (it, e_gpu, e_ref)      # exact arithmetic: same optimum value
         assert np.array_equal(got, lab), (it, int((got != lab).sum()))
         assert ch == ch_ref
     b.close()
 
 
-@pytest.mark.parametrize("H,W,K,diagonal", [(30, 45, 4, False), (50, 50, 7, True)])
-def test_component_pass_matches_move_model(H, W, K, diagonal):
+@pytest.mark.parametrize("H,W,K,diagonal,beta", [_as_before(30, 45, 4, False, 1.0), _as_before(50, 50, 7, True, 1.0),
+                                                 (30, 45, 4, False, 0.5), (50, 50, 7, True, 2.0)])
+def test_component_pass_matches_move_model(H, W, K, diagonal, beta):
     n, eid, w, lp, init = _integer_problem(6, H, W, K, diagonal)
     g = M.Graph(n, eid, w)
     b = _block(n, 2, K)
@@ -263,11 +306,11 @@ def test_component_pass_matches_move_model(H, W, K, diagonal):
     lab = init.astype(np.int64).copy()
     col, nc = M.icm_colours(H, W, diagonal)
     for _ in range(3):                       # a few ICM sweeps give blobs worth relabelling
-        M.icm_sweep(g, -lp, lab, 1.0, col, nc)
+        M.icm_sweep(g, -lp, lab, beta, col, nc)
     b.set_labels(lab)
     for it in range(3):
-        ch_ref = M.component_pass(g, -lp, lab, 1.0)
-        ch = b.component_pass(1.0)
+        ch_ref = M.component_pass(g, -lp, lab, beta)
+        ch = b.component_pass(beta)
         assert np.array_equal(b.get_labels(), lab), it
         assert ch == ch_ref
     b.close()
@@ -746,8 +789,9 @@ def test_full_size_cfg2_properties():
     b.close()
 
 
-@pytest.mark.parametrize("H,W,K,diagonal", [(48, 48, 6, True), (20, 130, 4, False)])
-def test_four_neighbour_grid_moves_and_solver(H, W, K, diagonal):
+@pytest.mark.parametrize("H,W,K,diagonal,beta", [_as_before(48, 48, 6, True, 1.0), _as_before(20, 130, 4, False, 1.0),
+                                                 (48, 48, 6, True, 0.5), (20, 130, 4, False, 2.0)])
+def test_four_neighbour_grid_moves_and_solver(H, W, K, diagonal, beta):
     """num_neighbor = 4 (the reference's other stencil, utility.py:1917-1920): the grid-native strip inputs carry zero
     diagonal weights; strip passes equal the move model, every move is energy-non-increasing, the solver converges."""
     rng = np.random.default_rng(H + W)
@@ -767,20 +811,20 @@ def test_four_neighbour_grid_moves_and_solver(H, W, K, diagonal):
     b.set_labels(init)
     lab = init.astype(np.int64).copy()
     for orient, sr, sc, alpha in [(0, 0, 0, -1), (1, 2, 9, 1), (0, 4, 33, 0), (1, 1, 0, -1)]:
-        prop = M.best_alternative(g, -lp, lab, 1.0) if alpha < 0 else np.full(n, alpha)
-        ch_ref = M.strip_fusion(g, -lp, lab, prop, 1.0, H, W, diagonal, orient, sr, sc)
-        ch = b.strip_pass(1.0, orient, sr, sc, alpha)
+        prop = M.best_alternative(g, -lp, lab, beta) if alpha < 0 else np.full(n, alpha)
+        ch_ref = M.strip_fusion(g, -lp, lab, prop, beta, H, W, diagonal, orient, sr, sc)
+        ch = b.strip_pass(beta, orient, sr, sc, alpha)
         got = b.get_labels().astype(np.int64)
         assert np.array_equal(got, lab) and ch == ch_ref, (orient, alpha, int((got != lab).sum()))
-    prev = b.energy(1.0)[0]
+    prev = b.energy(beta)[0]
     for fam in range(2):
-        b.chain_sweep(1.0, fam)
-        en = b.energy(1.0)[0]
+        b.chain_sweep(beta, fam)
+        en = b.energy(beta)[0]
         assert en <= prev + 1e-9
         prev = en
-    res = b.solve(1.0)
+    res = b.solve(beta)
     assert res["converged"] and res["energy"] <= prev + 1e-9
-    assert abs(res["energy"] - M.energy(g, -lp, b.get_labels().astype(np.int64), 1.0)[0]) < 1e-6
+    assert abs(res["energy"] - M.energy(g, -lp, b.get_labels().astype(np.int64), beta)[0]) < 1e-6
     b.close()
 
 
