@@ -48,9 +48,9 @@ typedef struct phmrf_block* phmrf_block_t;
 /* ---- library ---------------------------------------------------------------------------------- */
 /* ABI version = major * 100 + minor.  110 (round 4): PHMRF_NUM_KERNEL_CLASSES is 10 and phmrf_block_get_timing takes the
  * capacity of the caller's arrays; phmrf_block_get_work writes 8 values; the resumable solve (phmrf_mrf_solve_begin ...
- * _end) and the row-tile entry points are new.  120 (round 5): phmrf_block_get_work_first, phmrf_block_get_timing_first; phmrf_solve_opts.coarse_start.  121: phmrf_block_prepare_components.  122 (round 6): phmrf_block_get_work_ex.  123: phmrf_mrf_graph_expansion.  124: phmrf_mrf_solve_group.  125: phmrf_posterior_summary.  126: phmrf_smooth_labels.  A binding checks phmrf_version() == PHMRF_VERSION when it loads the library
+ * _end) and the row-tile entry points are new.  120 (round 5): phmrf_block_get_work_first, phmrf_block_get_timing_first; phmrf_solve_opts.coarse_start.  121: phmrf_block_prepare_components.  122 (round 6): phmrf_block_get_work_ex.  123: phmrf_mrf_graph_expansion.  124: phmrf_mrf_solve_group.  125: phmrf_posterior_summary.  126: phmrf_smooth_labels.  127: phmrf_filter_diffusion, phmrf_filter_bilateral, phmrf_filter_gaussian.  A binding checks phmrf_version() == PHMRF_VERSION when it loads the library
  * (phylo_hmrf_amd/_lib.py does). */
-#define PHMRF_VERSION 126
+#define PHMRF_VERSION 127
 PHMRF_API int phmrf_version(void);
 PHMRF_API const char* phmrf_last_error(void);
 PHMRF_API const char* phmrf_status_string(int status);
@@ -335,6 +335,37 @@ PHMRF_API int phmrf_posterior_summary(phmrf_block_t b, double beta, int estimate
  * PHMRF_ERR_UNSUPPORTED for K > 64 or n >= 2^31 - 64. */
 PHMRF_API int phmrf_smooth_labels(const uint8_t* labels_dev, uint8_t* out_dev, int H, int W, int diagonal, int K, int window,
                                   int64_t max_area, int n_iter, int64_t* counts_host, void* hip_stream);
+
+/* ---- pre-processing filters ----------------------------------------------------------------------- */
+/* ABI 127: the raw loader's smoothing filters (phylo_hmrf_amd/preprocess.py) on ONE H x W plane of a
+ * contact map, no block: row-major device buffers of H W pixels, pixel units throughout (sigmas, window and radius count
+ * pixels; sigma_color and kappa are in the image's own units, log(1 + normalised contact count) in the loader).  Each call
+ * is queued on hip_stream (NULL: the null stream) and returns when done.  All three: PHMRF_ERR_INVALID for a NULL buffer
+ * or H < 1 or W < 1, PHMRF_ERR_UNSUPPORTED for H W >= 2^31 - 64, PHMRF_ERR_HIP if a runtime call fails.
+ *
+ * phmrf_filter_diffusion: niter explicit Perona-Malik steps, the recurrence of preprocess.anisotropic_diffusion.  img_dev:
+ * float32 [H W], read and written (the result ends here); tmp_dev: float32 [H W] scratch, a buffer of its own.  Per step:
+ * forward differences d along both axes (0 at the far border), flux c(d) d with c = exp(-(d / kappa)^2) (option 1) or
+ * 1 / (1 + (d / kappa)^2) (option 2), backward difference of the flux, img += gamma * divergence.  kappa and gamma are
+ * rounded to float32 and every operation is a float32 one.  niter = 0 leaves img_dev untouched.  PHMRF_ERR_INVALID also
+ * for niter < 0 or an option other than 1 and 2. */
+PHMRF_API int phmrf_filter_diffusion(float* img_dev, float* tmp_dev, int64_t H, int64_t W, int niter, double kappa,
+                                     double gamma, int option, void* hip_stream);
+/* phmrf_filter_bilateral: the bilateral filter documented at the head of phmrf_bilateral (csrc/preprocess_host.cpp), the
+ * same tables and bins, float64 throughout.  img_dev: float64 [H W], read only; out_dev: float64 [H W], another buffer.
+ * win_size <= 0: max(5, 2 ceil(3 sigma_spatial) + 1) pixels; bins <= 0: 10000 entries of the colour table.  Pixels outside
+ * the image take part with value 0.  An image with min == max is copied.  PHMRF_ERR_INVALID also for a sigma <= 0, an even
+ * window, out_dev == img_dev, or an image with a negative value or a maximum of 0 (nothing written);
+ * PHMRF_ERR_UNSUPPORTED also for a window above 4095. */
+PHMRF_API int phmrf_filter_bilateral(const double* img_dev, double* out_dev, int64_t H, int64_t W, double sigma_color,
+                                     double sigma_spatial, int win_size, int bins, void* hip_stream);
+/* phmrf_filter_gaussian: scipy.ndimage.gaussian_filter(img, sigma, truncate=truncate) of a 2-D float64 image: axis 0 into
+ * tmp_dev, then axis 1 into out_dev; radius int(truncate sigma + 0.5) pixels, weights exp(-x^2 / (2 sigma^2)) normalised
+ * to sum 1, border mode `reflect` (d c b a | a b c d | d c b a) also where the radius exceeds the image.  img_dev: float64
+ * [H W], read only; out_dev, tmp_dev: float64 [H W], three different buffers.  PHMRF_ERR_INVALID also for sigma <= 0,
+ * truncate <= 0 or buffers that coincide; PHMRF_ERR_UNSUPPORTED also for a radius of 10^6 or more. */
+PHMRF_API int phmrf_filter_gaussian(const double* img_dev, double* out_dev, double* tmp_dev, int64_t H, int64_t W,
+                                    double sigma, double truncate, void* hip_stream);
 
 /* ---- initialisation --------------------------------------------------------- */
 /* One Lloyd step of k-means on the block's device-resident observations.  The reference initialises the states

@@ -96,6 +96,8 @@ def parse_args(argv=None):
     parser.add_option("--smooth_area", default="-1", help="--postprocess: largest area of a small region (-1: the reference's "
                       "80, or 25 for a region less than 100 bins high)")
     parser.add_option("--smooth_iter", default="1", help="--postprocess: number of smoothing passes")
+    parser.add_option("--filter_device", default="0", help="1: run the loader's smoothing filter (--filter_mode) on the GPU; "
+                      "0 (default): on the host.  Not with --reload 1, --synthetic or --postprocess, which filter nothing")
     parser.add_option("-h", "--help", action="help")
     opts, _ = parser.parse_args(argv)
     return opts
@@ -215,7 +217,14 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
         beta1, num_neighbor, filter_mode, conv_threshold, estimate_type, simu_version, annotation, reload_mode,
         diagonal_type, m_iter, resolution, quantile, ref_species, output_path, synthetic="0", seed="", quiet="0",
         init_method="minibatch", warm_start="best", checkpoint="", checkpoint_every="1", resume="", energy_tol_ppb="10000",
-        save_model="", segment="", postprocess="", smooth_window="5", smooth_area="-1", smooth_iter="1"):
+        save_model="", segment="", postprocess="", smooth_window="5", smooth_area="-1", smooth_iter="1",
+        filter_device="0"):
+    filter_device = int(filter_device)
+    if filter_device not in (0, 1):
+        raise SystemExit("--filter_device must be 0 or 1")
+    if filter_device and (int(reload_mode) == 1 or int(synthetic) > 0 or postprocess):
+        raise SystemExit("--filter_device 1 runs the raw loader's filter on the GPU: it cannot be combined with --reload 1, "
+                         "--synthetic or --postprocess, where nothing is filtered")
     if postprocess:
         from phylo_hmrf_amd.smooth import postprocess_file
         area = int(smooth_area)
@@ -303,7 +312,7 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
             print(x_max)
             samples, len_vec, edge_list_vec = preprocess.load_data_chromosome2(
                 chrom_vec, x_max, 0, resolution, num_neighbor, int(filter_mode), float(filter_sigma), int(diagonal_type),
-                ref_filename, filename_list, species, data_path, annotation)
+                ref_filename, filename_list, species, data_path, annotation, filter_device=bool(filter_device))
             write_cache(output_path, resolution, run_id, samples, edge_list_vec, len_vec)     # :1697-1704
     print("use time load data: %s" % (time.time() - start))
     print(samples.shape)
@@ -378,4 +387,4 @@ if __name__ == "__main__":
         checkpoint=opts.checkpoint, checkpoint_every=opts.checkpoint_every, resume=opts.resume,
         energy_tol_ppb=opts.energy_tol_ppb, save_model=opts.save_model, segment=opts.segment,
         postprocess=opts.postprocess, smooth_window=opts.smooth_window, smooth_area=opts.smooth_area,
-        smooth_iter=opts.smooth_iter)
+        smooth_iter=opts.smooth_iter, filter_device=opts.filter_device)

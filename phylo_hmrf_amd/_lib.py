@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PHMRF_LIB") or os.path.join(_HERE, "libphmrf.so")
 
 OK = 0
-ABI_VERSION = 126             # include/phmrf.h PHMRF_VERSION: checked against the library in load()
+ABI_VERSION = 127             # include/phmrf.h PHMRF_VERSION: checked against the library in load()
 NUM_KERNEL_CLASSES = 10
 # the per-block counter bank of a solve's round (include/phmrf.h, PHMRF_NUM_COUNTERS and the PHMRF_COUNTER_* slots:
 # tests/test_abi.py holds the two sides together): labels changed per move type
@@ -109,6 +109,9 @@ SIGNATURES = {
     "phmrf_posterior_stats_dev": [_vp, _d, _i, _vp],
     "phmrf_posterior_summary": [_vp, _d, _i, _fp, ctypes.POINTER(ctypes.c_uint8), _fp],
     "phmrf_smooth_labels": [_vp, _vp, _i, _i, _i, _i, _i, _i64, _i, _lp, _vp],
+    "phmrf_filter_diffusion": [_vp, _vp, _i64, _i64, _i, _d, _d, _i, _vp],
+    "phmrf_filter_bilateral": [_vp, _vp, _i64, _i64, _d, _d, _i, _i, _vp],
+    "phmrf_filter_gaussian": [_vp, _vp, _vp, _i64, _i64, _d, _d, _vp],
     "phmrf_kmeans_step": [_vp, _dp, _i, _dp],
     "phmrf_kmeans_moments": [_vp, _dp, _i, _dp],
     "phmrf_block_enable_timing": [_vp, _i],

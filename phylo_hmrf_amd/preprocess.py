@@ -23,6 +23,11 @@ rest of the pipeline is pinned on fixtures recorded from the reference's own loa
 skimage's `denoise_bilateral(img, sigma_color=0.5, sigma_spatial=5)` (:1575-1582): scikit-image is absent as well, so
 `denoise_bilateral` below restates its published algorithm (native, libphmrf_host.so) -- PARITY UNPINNED likewise.  Any
 other value with sigma > 0 is scipy's Gaussian filter, as in the reference.
+
+The three filters also run on the GPU (csrc/preprocess.hip): `anisotropic_diffusion_device`, `denoise_bilateral_device`
+and `gaussian_filter_device` have the signatures and results (to rounding) of their host twins, and
+`load_data_chromosome2(..., filter_device=True)` sends every region's planes through them.  They need the library and a
+GPU and raise without either: the loader never falls back to the host on its own.
 """
 from __future__ import print_function
 
@@ -108,26 +113,125 @@ def denoise_bilateral(img, sigma_color=None, sigma_spatial=1, win_size=None, bin
     return out
 
 
-def _apply_filter(mtx1, filter_mode, filter_param1, filter_param2, sigma):
-    """utility.py:1566-1588 / :1752-1774, channel by channel, in place."""
+class _DeviceScratch(object):
+    """The device buffers of one region's filtering: a plane's input, output and scratch buffers are allocated once and
+    shared by its channels (same shape and dtype -> the same buffer)."""
+
+    def __init__(self):
+        from . import _lib
+        import torch
+        self.lib = _lib.load()
+        _lib.require_gpu()
+        self.torch = torch
+        self.dev = torch.device("cuda", torch.cuda.current_device())
+        self.stream = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        self._bufs = {}
+
+    def buf(self, name, shape, dtype):
+        key = (name, dtype)
+        t = self._bufs.get(key)
+        if t is None or tuple(t.shape) != tuple(shape):
+            t = self._bufs[key] = self.torch.empty(tuple(shape), dtype=dtype, device=self.dev)
+        return t
+
+    def upload(self, name, plane):
+        """plane: C-contiguous NumPy array -> the device buffer `name` holding it"""
+        src = self.torch.from_numpy(plane)
+        t = self.buf(name, plane.shape, src.dtype)
+        t.copy_(src)
+        return t
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _check(status):
+    """a status of libphmrf.so -> ValueError for a refused argument, the binding's error for everything else"""
+    from . import _lib
+    if status in (1, 4):                                          # PHMRF_ERR_INVALID, PHMRF_ERR_UNSUPPORTED
+        raise ValueError(_lib.load().phmrf_last_error().decode())
+    _lib.check(status)
+
+
+def anisotropic_diffusion_device(img, niter=1, kappa=50, gamma=0.1, option=1, _scratch=None):
+    """`anisotropic_diffusion` of a 2-D image on the GPU (phmrf_filter_diffusion): the same float32 recurrence, one kernel
+    launch per iteration.  -> float32 array.  Raises without the library or a GPU."""
+    out = np.array(img, dtype=np.float32, copy=True, order="C")
+    if option not in (1, 2):
+        raise ValueError("option must be 1 or 2")
+    if out.ndim != 2:
+        raise ValueError("anisotropic_diffusion_device: a 2-D image (one channel) is expected")
+    sc = _scratch or _DeviceScratch()
+    if out.size == 0 or int(niter) <= 0:
+        return out
+    a = sc.upload("f32_img", out)
+    tmp = sc.buf("f32_tmp", out.shape, a.dtype)
+    _check(sc.lib.phmrf_filter_diffusion(_ptr(a), _ptr(tmp), out.shape[0], out.shape[1], int(niter), float(kappa),
+                                         float(gamma), int(option), sc.stream))
+    return a.cpu().numpy()
+
+
+def denoise_bilateral_device(img, sigma_color=None, sigma_spatial=1, win_size=None, bins=10000, _scratch=None):
+    """`denoise_bilateral` on the GPU (phmrf_filter_bilateral): the same tables, bins and float64 sums, so the two agree to
+    the rounding of the summation order.  -> float64 array.  Raises without the library or a GPU."""
+    a = np.ascontiguousarray(img, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError("denoise_bilateral: a 2-D image (one channel) is expected")
+    if sigma_color is None:
+        sigma_color = float(a.std())                              # skimage: `sigma_color or image.std()`
+    sc = _scratch or _DeviceScratch()
+    src = sc.upload("f64_img", a)
+    dst = sc.buf("f64_out", a.shape, src.dtype)
+    st = sc.lib.phmrf_filter_bilateral(_ptr(src), _ptr(dst), a.shape[0], a.shape[1], float(sigma_color), float(sigma_spatial),
+                                       0 if win_size is None else int(win_size), int(bins), sc.stream)
+    if st == 1:
+        raise ValueError("denoise_bilateral: image must contain only positive values, sigmas must be positive, the "
+                         "window odd")
+    _check(st)
+    return dst.cpu().numpy()
+
+
+def gaussian_filter_device(img, sigma, _scratch=None):
+    """`scipy.ndimage.gaussian_filter(img, sigma)` of a 2-D float64 image on the GPU (phmrf_filter_gaussian: separable,
+    truncate 4, border mode reflect).  -> float64 array.  Raises without the library or a GPU."""
+    a = np.ascontiguousarray(img, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError("gaussian_filter_device: a 2-D image (one channel) is expected")
+    sc = _scratch or _DeviceScratch()
+    src = sc.upload("f64_img", a)
+    dst = sc.buf("f64_out", a.shape, src.dtype)
+    tmp = sc.buf("f64_tmp", a.shape, src.dtype)
+    _check(sc.lib.phmrf_filter_gaussian(_ptr(src), _ptr(dst), _ptr(tmp), a.shape[0], a.shape[1], float(sigma), 4.0,
+                                        sc.stream))
+    return dst.cpu().numpy()
+
+
+def _apply_filter(mtx1, filter_mode, filter_param1, filter_param2, sigma, device=False):
+    """utility.py:1566-1588 / :1752-1774, channel by channel, in place.  device=True: the same filters on the GPU, the
+    region's device buffers shared by its channels; no fallback to the host."""
     dim1 = mtx1.shape[-1]
+    if device:
+        diffusion, bilateral, gaussian = anisotropic_diffusion_device, denoise_bilateral_device, gaussian_filter_device
+        kw = dict(_scratch=_DeviceScratch())
+    else:
+        import scipy.ndimage
+        diffusion, bilateral, gaussian, kw = anisotropic_diffusion, denoise_bilateral, scipy.ndimage.gaussian_filter, {}
     if filter_mode == 0:
         for i in range(dim1):
             if filter_param1 < 0:
-                mtx1[:, :, i] = anisotropic_diffusion(mtx1[:, :, i], niter=10, kappa=50, gamma=0.1, option=1)
+                mtx1[:, :, i] = diffusion(mtx1[:, :, i], niter=10, kappa=50, gamma=0.1, option=1, **kw)
             else:
-                mtx1[:, :, i] = anisotropic_diffusion(mtx1[:, :, i], niter=filter_param1, kappa=filter_param2, gamma=0.1,
-                                                      option=1)
+                mtx1[:, :, i] = diffusion(mtx1[:, :, i], niter=filter_param1, kappa=filter_param2, gamma=0.1, option=1, **kw)
     elif filter_mode == 1:
         for i in range(dim1):
             if filter_param1 < 0:
-                mtx1[:, :, i] = denoise_bilateral(mtx1[:, :, i], sigma_color=0.5, sigma_spatial=5)
+                mtx1[:, :, i] = bilateral(mtx1[:, :, i], sigma_color=0.5, sigma_spatial=5, **kw)
             else:
-                mtx1[:, :, i] = denoise_bilateral(mtx1[:, :, i], sigma_color=filter_param1, sigma_spatial=filter_param2)
+                mtx1[:, :, i] = bilateral(mtx1[:, :, i], sigma_color=filter_param1, sigma_spatial=filter_param2, **kw)
     elif sigma > 0:
-        import scipy.ndimage
         for i in range(dim1):
-            mtx1[:, :, i] = scipy.ndimage.gaussian_filter(mtx1[:, :, i], sigma)
+            mtx1[:, :, i] = gaussian(mtx1[:, :, i], sigma, **kw)
 
 
 # ---- merge of the species' contact files -----------------------------------------------------------------------
@@ -262,7 +366,8 @@ def grid_edges(X, H, W, diagonal, num_neighbor=8):
     return _ge(X, H, W, diagonal, num_neighbor)
 
 
-def _region_block(region, x, position, resolution, num_neighbor, filter_mode, filter_param1, filter_param2, sigma):
+def _region_block(region, x, position, resolution, num_neighbor, filter_mode, filter_param1, filter_param2, sigma,
+                  filter_device=False):
     """load_data_chromosome_sub3 (utility.py:470-534) for one region -> (samples, t_lenvec (8 fields), edge_list)."""
     position1, position2, position1a, position2a = region[0:4]
     region_id1 = region[6]
@@ -283,7 +388,7 @@ def _region_block(region, x, position, resolution, num_neighbor, filter_mode, fi
             plane = np.ascontiguousarray(mtx1[:, :, s])
             median_fill(plane, True)
             mtx1[:, :, s] = plane
-        _apply_filter(mtx1, filter_mode, filter_param1, filter_param2, sigma)
+        _apply_filter(mtx1, filter_mode, filter_param1, filter_param2, sigma, device=filter_device)
         ii, jj = np.triu_indices(win)                                                      # :2310-2317
         data1 = mtx1[ii, jj, :]
         edges = grid_edges(data1, win, win, True, num_neighbor)
@@ -298,14 +403,16 @@ def _region_block(region, x, position, resolution, num_neighbor, filter_mode, fi
             plane = np.ascontiguousarray(mtx1[:, :, s])
             median_fill(plane, False)
             mtx1[:, :, s] = plane
-        _apply_filter(mtx1, filter_mode, filter_param1, filter_param2, sigma)
+        _apply_filter(mtx1, filter_mode, filter_param1, filter_param2, sigma, device=filter_device)
         data1 = mtx1.reshape(H * W, S).copy()
         edges = grid_edges(data1, H, W, False, num_neighbor)
     return data1, [data1.shape[0], H, W, start1, start2, region_id1, type_id1, region[8]], edges
 
 
 def load_data_chromosome2(chrom_vec, x_max, x_min, resolution, num_neighbor, filter_mode, sigma, diagonal_typeId,
-                          ref_filename, filename_list, species, data_path, annotation=""):
+                          ref_filename, filename_list, species, data_path, annotation="", filter_device=False):
+    """filter_device=True runs the smoothing filter of every region on the GPU (the `*_device` functions above; RuntimeError
+    without one); everything else, and every result with the default, is the host's."""
     samples, len_vec, edge_list_vec = [], [], []
     offset = 0
     filter_param1, filter_param2 = (5, 50) if filter_mode == 0 else (-1, -1)               # utility.py:411-412
@@ -319,7 +426,7 @@ def load_data_chromosome2(chrom_vec, x_max, x_min, resolution, num_neighbor, fil
             regions = [r for r in regions if r[0] == r[2] and r[1] == r[3]]               # :396-400
         for region in regions:
             data1, lv, edges = _region_block(region, x, position, resolution, num_neighbor, filter_mode, filter_param1,
-                                             filter_param2, sigma)
+                                             filter_param2, sigma, filter_device)
             n = data1.shape[0]
             lv[1:1] = [offset, offset + n]                                                 # :453-454, :322-324
             offset += n
