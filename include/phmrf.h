@@ -263,7 +263,9 @@ PHMRF_API int phmrf_mrf_component_pass(phmrf_block_t b, double beta, int64_t* ch
  * minimum s-t cut on the device (maxflow.hip: lock-free push-relabel with global relabelling, capacities quantised with the
  * largest term at 2^24 as gco's finest quantisation).  The move gco's expansion() makes (GCoptimization.cpp:1120-1280) on a
  * general graph (GCoptimization.h:551-597); phmrf_mrf_solve runs it for every label on blocks without grid geometry, where
- * the strip moves do not exist.  Works on any block with a graph; *changed = labels that took alpha. */
+ * the strip moves do not exist.  Works on any block with a graph; *changed = labels that took alpha.  The flow may take
+ * 64 + n / 6 relabelling rounds of 24 sweeps; one that has not ended by then makes no move and returns
+ * PHMRF_ERR_UNSUPPORTED (here and from a solve alike), never PHMRF_OK with *changed = 0. */
 PHMRF_API int phmrf_mrf_graph_expansion(phmrf_block_t b, double beta, int alpha, int64_t* changed);
 /* Optional scheduling hint: queue, on the block's stream, the part of the next component pass that depends on the labels
  * alone (the connected components of equal label).  The EM driver calls it between two E-steps, where the GPU would

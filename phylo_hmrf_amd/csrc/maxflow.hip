@@ -18,13 +18,25 @@
 // GCoptimization.h:139-143) -- so pushes are exact and the algorithm ends; a node's switch cost is rounded UP by one
 // quantum so that ties keep the label.
 //
-// The flow.  push_relabel_kernel: every active node with excess and height < n pushes to the sink first, then to its
+// The flow.  push_relabel_kernel: every active node with excess and height <= n pushes to the sink first, then to its
 // lowest residual neighbour if that is lower, else lifts itself above it (atomics on the neighbour's excess and on the
 // reverse arc only).  Excess that no sink can take is trapped among the nodes that WILL switch; instead of lifting them
-// to n one step at a time, a global relabelling every PR_SWEEPS sweeps sets every node's height to its residual distance
-// to the sink (level-synchronous BFS; most nodes have a sink arc, so the BFS only has to walk into the pockets) and n where
-// there is no path.  The move: the nodes that cannot reach the sink take alpha.  Energy non-increasing up to the
-// quantisation (1e-7 of the largest term per node); the solver's round energies are f64 and judge it.
+// up one step at a time, a global relabelling every PR_SWEEPS sweeps sets every node's height to its residual distance
+// to the sink (level-synchronous BFS; most nodes have a sink arc, so the BFS only has to walk into the pockets) and n + 1
+// where there is no path.  (A node with a sink arc is at level 1, so the far end of a path of n active nodes is at level n:
+// "cannot reach the sink" must be a height no level can take, unreachable() = n + 1.)  The move: the nodes that cannot
+// reach the sink take alpha.
+//
+// The rounds.  Every sweep in which a node with excess can still reach the sink pushes or lifts at least once, so the
+// flow always ends; with exact heights excess moves about one hop per sweep, so the rounds an expansion may take grow
+// with n (round_limit: 64 + n / 6 rounds of 24 sweeps, four sweeps per node over the first 1,536).  An expansion that is
+// still unfinished then is an ERROR (PHMRF_ERR_UNSUPPORTED, for the direct call and inside a solve alike), never a
+// silent "no move": a caller could not tell that from "alpha has nothing to gain".
+//
+// The quantisation.  Pair capacities are truncated, switch costs rounded up plus one quantum q = top / 2^24.  Against the
+// exact optimum S* the chosen set S can lose 2 q per node of S* \ S and q per arc that only S cuts, plus the float32
+// rounding of theta and of the capacities (tests/maxflow_reference.py: expansion_allowance derives the bound term by term,
+// tests/test_gpu_maxflow.py holds the kernels to it); the solver's round energies are f64 and judge the move.
 
 #include <algorithm>
 #include <vector>
@@ -36,8 +48,13 @@ namespace {
 
 constexpr int PR_SWEEPS = 24;          // push-relabel sweeps between two global relabellings
 constexpr int BFS_LEVELS = 12;         // BFS levels queued per look at the "changed" flag
-constexpr int MAX_ROUNDS = 64;         // (sweeps + relabelling) rounds before an expansion is given up (no move)
+constexpr int MIN_ROUNDS = 64;         // (sweeps + relabelling) rounds every expansion may take ...
+constexpr int ROUND_NODES = 6;         // ... and one more per ROUND_NODES nodes: PR_SWEEPS / ROUND_NODES = 4 sweeps per node
 constexpr float CAP_SCALE_TOP = 16777216.f;      // 2^24
+
+// the height of a node without a residual path to the sink, and of the nodes that are alpha already: above every BFS level
+// (levels run from 1 to the number of active nodes <= n)
+__host__ __device__ inline int32_t unreachable(int64_t n) { return (int32_t)n + 1; }
 
 struct MfPtrs {
   int64_t n;
@@ -103,14 +120,18 @@ __global__ __launch_bounds__(256) void mf_quantise_kernel(MfPtrs p, float beta, 
     const long long q = act ? (long long)ceilf(scale * p.theta[i]) + 1ll : 0ll;
     p.tcap[i] = q > 0 ? (int32_t)(q > 2000000000ll ? 2000000000ll : q) : 0;
     p.exc[i] = q < 0 ? -q : 0ll;
-    p.hgt[i] = act ? 0 : (int32_t)p.n;
+    p.hgt[i] = act ? 0 : unreachable(p.n);
   }
 }
 
 // one sweep of the lock-free push-relabel (Hong 2008; He & Hong 2010): correct with stale heights, atomics on the excess of
-// the receiving node and on the reverse arc only
+// the receiving node and on the reverse arc only.
+// The plain store to cu[amin] is safe: the only other writer of the arc u -> v is v, when it pushes to u (its reverse arc).
+// u pushes to v only if it read h(u) > h(v), v to u only if it read h(v) > h(u); heights change in a sweep only by the
+// nodes that lift themselves, and a node that pushes does not lift itself in that sweep, so h(u) and h(v) would both be
+// what the other read: both ends of an arc cannot push along it in the same sweep.
 __global__ __launch_bounds__(256) void mf_push_relabel_kernel(MfPtrs p) {
-  const int32_t nn = (int32_t)p.n;
+  const int32_t nn = unreachable(p.n);
   for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < p.n; u += (int64_t)gridDim.x * blockDim.x) {
     long long e = p.exc[u];
     const int32_t hu = p.hgt[u];
@@ -157,7 +178,7 @@ constexpr int32_t UNSEEN = 0x7ffffff0;
 __global__ __launch_bounds__(256) void mf_bfs_init_kernel(MfPtrs p, int alpha) {
   for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < p.n; u += (int64_t)gridDim.x * blockDim.x) {
     const bool act = p.labels[u] != alpha;
-    p.hgt[u] = !act ? (int32_t)p.n : (p.tcap[u] > 0 ? 1 : UNSEEN);
+    p.hgt[u] = !act ? unreachable(p.n) : (p.tcap[u] > 0 ? 1 : UNSEEN);
   }
 }
 
@@ -183,7 +204,7 @@ __global__ __launch_bounds__(256) void mf_bfs_level_kernel(MfPtrs p, int level, 
 
 __global__ __launch_bounds__(256) void mf_bfs_finish_kernel(MfPtrs p) {
   int cnt = 0;
-  const int32_t nn = (int32_t)p.n;
+  const int32_t nn = unreachable(p.n);
   for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < p.n; u += (int64_t)gridDim.x * blockDim.x) {
     int32_t h = p.hgt[u];
     if (h == UNSEEN) p.hgt[u] = h = nn;                      // no residual path to the sink
@@ -197,7 +218,7 @@ __global__ __launch_bounds__(256) void mf_bfs_finish_kernel(MfPtrs p) {
 __global__ __launch_bounds__(256) void mf_apply_kernel(MfPtrs p, int alpha, unsigned long long* __restrict__ changed,
                                                        uint16_t* __restrict__ stamp, int tick) {
   unsigned int mine = 0u;
-  const int32_t nn = (int32_t)p.n;
+  const int32_t nn = unreachable(p.n);
   for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < p.n; u += (int64_t)gridDim.x * blockDim.x) {
     if (p.labels[u] == alpha || p.hgt[u] < nn) continue;     // (an active node that cannot reach the sink takes alpha)
     p.labels[u] = (uint8_t)alpha;
@@ -273,7 +294,8 @@ int launch_graph_expansion(phmrf_block* b, float beta, int alpha) {
   hipLaunchKernelGGL(mf_theta_kernel, dim3(grid), dim3(256), 0, st, p, beta, alpha);
   hipLaunchKernelGGL(mf_quantise_kernel, dim3(grid), dim3(256), 0, st, p, beta, alpha);
   bool done = false;
-  for (int round = 0; round < MAX_ROUNDS && !done; ++round) {
+  const int64_t round_limit = MIN_ROUNDS + n / ROUND_NODES;
+  for (int64_t round = 0; round < round_limit && !done; ++round) {
     for (int sw = 0; sw < PR_SWEEPS; ++sw) hipLaunchKernelGGL(mf_push_relabel_kernel, dim3(grid), dim3(256), 0, st, p);
     // global relabelling: BFS from the sink, BFS_LEVELS levels per look at the flag
     PHMRF_HIP(hipMemsetAsync(b->mf_flags + 1, 0, 2 * sizeof(int32_t), st));
@@ -284,7 +306,8 @@ int launch_graph_expansion(phmrf_block* b, float beta, int alpha) {
       for (int q = 0; q < BFS_LEVELS; ++q, ++level) hipLaunchKernelGGL(mf_bfs_level_kernel, dim3(grid), dim3(256), 0, st, p, level, gate);
       PHMRF_HIP(hipMemcpyAsync(b->mf_flags_host, b->mf_flags, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
       PHMRF_HIP(hipStreamSynchronize(st));
-      if (b->mf_flags_host[1] < level - 1 || level > n + 2) break;        // the last queued level labelled nothing
+      // the last queued level labelled nothing (or, as a guard: past unreachable(n), above which no level exists)
+      if (b->mf_flags_host[1] < level - 1 || level > (int64_t)unreachable(n) + 1) break;
     }
     hipLaunchKernelGGL(mf_bfs_finish_kernel, dim3(grid), dim3(256), 0, st, p);
     PHMRF_HIP(hipMemcpyAsync(b->mf_flags_host, b->mf_flags, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -292,7 +315,8 @@ int launch_graph_expansion(phmrf_block* b, float beta, int alpha) {
     done = b->mf_flags_host[2] == 0;                                       // no node with excess can still reach the sink
   }
   PHMRF_HIP(hipGetLastError());
-  if (!done) return PHMRF_OK;                                             // (given up: no move; the other move types go on)
+  if (!done)
+    return fail(PHMRF_ERR_UNSUPPORTED, "graph expansion: the flow did not end within 64 + n / 6 relabelling rounds (no move was made)");
   hipLaunchKernelGGL(mf_apply_kernel, dim3(grid), dim3(256), 0, st, p, alpha, b->counters + b->counter_slot,
                      b->tick ? b->stamp : nullptr, b->tick);
   PHMRF_HIP(hipGetLastError());
