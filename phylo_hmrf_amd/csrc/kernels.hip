@@ -820,8 +820,11 @@ int launch_posterior_s(const phmrf_block* b, float beta, int estimate_type, bool
   double* partial = b->deterministic ? b->post_partial : nullptr;
   int TB = partial ? POST_DET_TB : (tb_env == 64 || tb_env == 128 || tb_env == 256) ? tb_env : 256;
   const size_t acc_bytes = (size_t)K * M * sizeof(double);            // the workgroup's f64 statistics
-  // (the tile prefers 64 KB, which leaves two workgroups per CU; K and S at their limits -- K = 64, S = 8: 72 KB at 64 rows --
-  //  take a larger share of the CU's 160 KB instead of being refused)
+  // (the tile stays under 64 KB, which leaves two workgroups per CU: only [1 | x] per node is in LDS, so K and S at their limits
+  //  -- K = 64, S = 8: 128 rows x (65 + 9) floats + 64 x 45 doubles = 59.5 KB -- fit at 128 rows; K >= 40 at S = 8 down to K >= 60 at
+  //  S = 1 run 128 rows, smaller shapes 256; 64 rows run only where they are asked for: the deterministic mode, and
+  //  PHMRF_POST_TB=64 in the development library.  At 64 rows the largest shape takes 41.3 KB, so with K <= 64 and S <= 8
+  //  the size check below and the hipFuncSetAttribute branch of the launch cannot be reached: they guard wider limits)
   while (TB > 64 && (size_t)TB * (Kp + Mp) * sizeof(float) + acc_bytes > 64 * 1024 - 256) TB >>= 1;
   PHMRF_CHECK((size_t)TB * (Kp + Mp) * sizeof(float) + acc_bytes <= 158 * 1024, PHMRF_ERR_UNSUPPORTED,
               "posterior_stats: K and S too large for the LDS tile");

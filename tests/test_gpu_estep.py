@@ -44,7 +44,9 @@ def test_emission_golden(tag):
     b.close()
 
 
-@pytest.mark.parametrize("S,K,n", [(4, 10, 70001), (4, 20, 4099), (8, 30, 5000), (3, 7, 1000), (4, 64, 777), (1, 1, 5)])
+@pytest.mark.parametrize("S,K,n", [(4, 10, 70001), (4, 20, 4099), (8, 30, 5000), (3, 7, 1000), (4, 64, 777), (1, 1, 5),
+                                   (2, 9, 1031), (5, 64, 517), (6, 11, 1031), (7, 64, 517), (9, 13, 1031), (12, 64, 517), (16, 15, 1031),
+                                   (2, 64, 300), (6, 64, 300), (9, 64, 300), (16, 64, 300), (5, 5, 1031), (7, 3, 1031), (12, 7, 1031)])
 def test_emission_oracle_shapes(S, K, n):
     rng = np.random.default_rng(S * 100 + K)
     A = rng.standard_normal((K, S, S))
@@ -624,7 +626,7 @@ def test_posterior_stats_golden(et):
     b.close()
 
 
-# (the last two: the kernel's corner -- K = 64, S = 8 takes 158 KB of the CU's 160 KB of LDS at 64-node tiles; K = 56 the size below)
+# (the last two: the kernel's corner -- K = 64, S = 8 takes 59.5 KB of LDS at 128-node tiles; K = 56 the size below, 52.7 KB)
 @pytest.mark.parametrize("S,K,N", [(4, 20, 120), (8, 30, 60), (4, 10, 200), (8, 64, 50), (8, 56, 50)])
 def test_posterior_stats_oracle(S, K, N):
     blk = synth.make_block(5, N, N, S, K, True)
