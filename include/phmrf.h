@@ -374,7 +374,11 @@ PHMRF_API int phmrf_filter_gaussian(const double* img_dev, double* out_dev, doub
  * with sklearn's MiniBatchKMeans on the host (phylo_hmrf.py:234-238); this keeps X where it is.  Every node goes to
  * its nearest centre (squared Euclidean distance, lowest index on ties).
  *   out[0 .. K*S)        per-cluster sums of x        out[K*S .. K*S+K)  cluster sizes        out[K*S+K]  inertia
- * write_labels != 0: the assignment becomes the block's labels (the reference's init_label, :241-244).            */
+ * write_labels != 0: the assignment becomes the block's labels (the reference's init_label, :241-244).
+ * PHMRF_ERR_INVALID for a non-finite centre, PHMRF_ERR_STATE without observations.  The observations are NOT inspected:
+ * they must be finite with |x_s - c_ks| <= 4e18 in every coordinate.  Beyond that (an f32 squared distance of 3.0e38 or
+ * more, or NaN, to every centre) a node gets label 0 and the inertia is meaningless -- no error is reported.
+ * A row tile labels all its nodes and counts the owned rows only.                                                  */
 PHMRF_API int phmrf_kmeans_step(phmrf_block_t b, const double* centers /* [K,S] */, int write_labels,
                                 double* out /* [K*S + K + 1] */);
 
@@ -382,7 +386,8 @@ PHMRF_API int phmrf_kmeans_step(phmrf_block_t b, const double* centers /* [K,S] 
  *   out[K*S+K+1 .. +K*S*S)  sum over the cluster's nodes of x x^T.
  * With the sums and the counts that is everything the reference's initialisation takes from the observations after
  * clustering: the per-cluster OU fit works on a cluster's mean and X^T X / n (phylo_hmrf.py:1246-1325, :1427-1498) and
- * the first covariance is the global one (:258) -- so no host pass over the observations is left.                   */
+ * the first covariance is the global one (:258) -- so no host pass over the observations is left.
+ * PHMRF_ERR_UNSUPPORTED for S > 8; otherwise the errors and the admitted range of phmrf_kmeans_step.               */
 PHMRF_API int phmrf_kmeans_moments(phmrf_block_t b, const double* centers /* [K,S] */, int write_labels,
                                    double* out /* [K*S + K + 1 + K*S*S] */);
 

@@ -7,6 +7,13 @@
 // One thread per node, centres via wave-uniform scalar loads (K*S floats), per-workgroup partial sums in LDS (f32 within
 // a tile of 256 nodes), f64 atomics across workgroups -- the accumulation scheme of the posterior kernel.
 // HBM-bound: 4S bytes per node in, 1 byte out.
+//
+// Admitted range: the running minimum starts at 3.0e38f, so a node is assigned by distance only while one of its f32
+// squared distances is below that -- guaranteed for |x_s - c_ks| <= 4e18 in every coordinate (S <= 16).  The API rejects
+// non-finite centres; the observations are not inspected.  A node whose distances are all >= 3.0e38f or NaN (a non-finite
+// or absurdly large observation) silently gets label 0 and adds 3.0e38f to the inertia: finite observations within that
+// range are the caller's side of the contract (include/phmrf.h, phmrf_kmeans_step).
+// Exactness and error bounds of every output: tests/kmeans_reference.py.
 
 #include "common.h"
 
