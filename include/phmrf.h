@@ -318,9 +318,30 @@ PHMRF_API int phmrf_posterior_stats_dev(phmrf_block_t b, double beta, int estima
  *   conf[i]    = post[i, l_i]                 host float32 [owned]: bit for bit what phmrf_posterior_stats computes
  *   top[i]     = argmax_k post[i, k]          host uint8 [owned]: the lowest k on ties
  *   entropy[i] = -sum_k post log post (nats)  host float32 [owned]; entropy_or_null == NULL skips it
- * Needs labels, logprob and a graph (PHMRF_ERR_STATE otherwise); estimate_type as in phmrf_posterior_stats. */
+ * Needs labels, logprob and a graph (PHMRF_ERR_STATE otherwise); estimate_type as in phmrf_posterior_stats.  With block
+ * timing on, the kernel is counted in the class posterior_stats. */
 PHMRF_API int phmrf_posterior_summary(phmrf_block_t b, double beta, int estimate_type, float* conf, uint8_t* top,
                                       float* entropy_or_null);
+
+/* Posterior-weighted affine maps of the observations, for reconstructing ancestral contact maps from a fitted model
+ * (no ABI bump: the call only adds an entry point).  Nothing here is tied to a tree: the caller
+ * gives, per state k and output a, an affine map mu_ka(x) = c_ka + g_ka . x of the node's S observations and a variance
+ * v_ka, and gets per OWNED node i (all n unless the block is a row tile), with p_ik the conditional posterior of
+ * phmrf_posterior_stats / phmrf_posterior_summary given the neighbours' current labels:
+ *   weighting 0 (posterior)  mean[a, i] = sum_k p_ik mu_ka(x_i)
+ *                            sd[a, i]^2 = sum_k p_ik v_ka + sum_k p_ik (mu_ka(x_i) - mean[a, i])^2   (computed in this form)
+ *   weighting 1 (called)     mean[a, i] = mu_{l_i,a}(x_i),   sd[a, i]^2 = v_{l_i,a}
+ *   affine    host float64 [K, A, S+1]: c_ka, then g_ka[0..S)      cond_var  host float64 [K, A]: v_ka
+ *   mean_out  host float32 [A, owned], output-major planes          sd_out_or_null  the same shape, NULL skips it
+ * Units: those of the block's observations (for a model fitted by this package the loader's normalised features, not raw
+ * contact counts).  The tables are rounded to float32 and every operation is a float32 one; no atomics, so two calls on
+ * the same inputs give the same bits, and mean_out does not depend on whether sd is asked for.  With block timing on, the
+ * kernel is counted in the class posterior_stats.
+ * PHMRF_ERR_INVALID for a NULL argument, a weighting other than 0 and 1, a table entry that is not finite (as float32) or a
+ * negative cond_var; PHMRF_ERR_UNSUPPORTED for A outside [1, 16] or S > 8; PHMRF_ERR_STATE without observations, without
+ * labels or (weighting 0 only) without logprob and a graph.  estimate_type as in phmrf_posterior_stats. */
+PHMRF_API int phmrf_ancestral(phmrf_block_t b, double beta, int estimate_type, int weighting, int A, const double* affine,
+                              const double* cond_var, float* mean_out, float* sd_out_or_null);
 
 /* ---- post-processing ---------------------------------------------------------------------------- */
 /* ABI 126: the reference's small-region smoothing of a state map (processing/small_region_test.m) on

@@ -89,6 +89,9 @@ def parse_args(argv=None):
                       "solver and preprocessing settings) to this .npz, for --segment")
     parser.add_option("--segment", default="", help="skip the fit: segment the data with the model saved at this path (cold "
                       "solve from argmax, per-bin confidence) and write segment_<run_id>_<K>.mat")
+    parser.add_option("--ancestral", default="", help="with --segment: after the segmentation, reconstruct the contact map of "
+                      "every internal tree node (posterior: weighted by the state posteriors; called: the called state's own "
+                      "map) with its standard deviation, in the model's feature units, and write ancestral_<run_id>_<K>.npz")
     parser.add_option("--postprocess", default="", help="skip loading data and fitting: smooth the states of this "
                       "estimate_ou_*.mat or segment_*.mat (the reference's processing/*.m), write estimate_test<chrom>.ori.txt, "
                       ".smooth.txt and test<chrom>.region.txt in genome coordinates (--resolution) and smooth_<stem>.mat under --output")
@@ -212,13 +215,27 @@ def segment_settings(m, num_states, resolution, num_neighbor, filter_mode, filte
     return (out["num_states"], out["resolution"], out["num_neighbor"], out["filter_mode"], out["filter_sigma"], out["dtype"])
 
 
+def check_ancestral(ancestral, segment, postprocess):
+    """--ancestral posterior|called reconstructs on a segmentation's labels: only together with --segment"""
+    if not ancestral:
+        return
+    if ancestral not in ("posterior", "called"):
+        raise SystemExit("--ancestral must be posterior or called, not %r (it goes with --segment)" % (ancestral,))
+    if postprocess:
+        raise SystemExit("--ancestral cannot be combined with --postprocess, which loads no data: it goes with --segment")
+    if not segment:
+        raise SystemExit("--ancestral needs --segment: the ancestors are reconstructed with a saved model on the labels of "
+                         "its segmentation")
+
+
 def run(num_states, chromvec, root_path, multiple, species_name, sort_states, run_id1, cons_param, method_mode,
         initial_mode, initial_weight, initial_weight1, initial_magnitude, position1, position2, filter_sigma, beta,
         beta1, num_neighbor, filter_mode, conv_threshold, estimate_type, simu_version, annotation, reload_mode,
         diagonal_type, m_iter, resolution, quantile, ref_species, output_path, synthetic="0", seed="", quiet="0",
         init_method="minibatch", warm_start="best", checkpoint="", checkpoint_every="1", resume="", energy_tol_ppb="10000",
         save_model="", segment="", postprocess="", smooth_window="5", smooth_area="-1", smooth_iter="1",
-        filter_device="0"):
+        filter_device="0", ancestral=""):
+    check_ancestral(ancestral, segment, postprocess)
     filter_device = int(filter_device)
     if filter_device not in (0, 1):
         raise SystemExit("--filter_device must be 0 or 1")
@@ -329,6 +346,14 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
         if rank == 0:
             scipy.io.savemat(filename3, {"state_vec": res["state_vec"], "len_vec": np.asarray(len_vec), "conf": res["conf"],
                                          "top": res["top"], "energy": res["energy"]})
+        if ancestral:
+            from phylo_hmrf_amd.ancestral import save_npz
+            start = time.time()
+            anc = model.ancestral(weighting=ancestral)
+            print("ancestral use time: %s %s" % (time.time() - start, anc["timing"]))
+            if rank == 0:
+                leaves = species if species is not None else seg_model.species
+                save_npz("%s/ancestral_%d_%d.npz" % (output_path, run_id, n_components1), anc, ancestral, len_vec, leaves)
         model.close()
         if world > 1:
             import torch.distributed as dist
@@ -387,4 +412,4 @@ if __name__ == "__main__":
         checkpoint=opts.checkpoint, checkpoint_every=opts.checkpoint_every, resume=opts.resume,
         energy_tol_ppb=opts.energy_tol_ppb, save_model=opts.save_model, segment=opts.segment,
         postprocess=opts.postprocess, smooth_window=opts.smooth_window, smooth_area=opts.smooth_area,
-        smooth_iter=opts.smooth_iter, filter_device=opts.filter_device)
+        smooth_iter=opts.smooth_iter, filter_device=opts.filter_device, ancestral=opts.ancestral)

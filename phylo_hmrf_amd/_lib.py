@@ -108,6 +108,7 @@ SIGNATURES = {
     "phmrf_posterior_stats": [_vp, _d, _i, _dp, _dp, _dp],
     "phmrf_posterior_stats_dev": [_vp, _d, _i, _vp],
     "phmrf_posterior_summary": [_vp, _d, _i, _fp, ctypes.POINTER(ctypes.c_uint8), _fp],
+    "phmrf_ancestral": [_vp, _d, _i, _i, _i, _dp, _dp, _fp, _fp],
     "phmrf_smooth_labels": [_vp, _vp, _i, _i, _i, _i, _i, _i64, _i, _lp, _vp],
     "phmrf_filter_diffusion": [_vp, _vp, _i64, _i64, _i, _d, _d, _i, _vp],
     "phmrf_filter_bilateral": [_vp, _vp, _i64, _i64, _d, _d, _i, _i, _vp],

@@ -303,6 +303,26 @@ class Block(object):
                                               ent.ctypes.data_as(fp) if want_entropy else None))
         return conf, top, ent
 
+    WEIGHTINGS = ("posterior", "called")
+
+    def ancestral(self, beta, estimate_type, affine, cond_var, weighting="posterior", want_sd=True):
+        """posterior-weighted (or the called state's) affine maps of the observations per owned node (include/phmrf.h,
+        phmrf_ancestral): affine [K, A, S+1] (c, then the row of G), cond_var [K, A] -> (mean float32 [A, owned], sd float32
+        [A, owned] or None), in the units of the observations"""
+        if weighting not in self.WEIGHTINGS:
+            raise ValueError("weighting must be one of %s, not %r" % (", ".join(self.WEIGHTINGS), weighting))
+        aff, cv = as_f64(affine), as_f64(cond_var)
+        if aff.ndim != 3 or aff.shape[0] != self.K or aff.shape[2] != self.S + 1 or cv.shape != aff.shape[:2]:
+            raise ValueError("affine %s / cond_var %s are not [K = %d, A, S + 1 = %d] / [K, A]"
+                             % (aff.shape, cv.shape, self.K, self.S + 1))
+        A, m = aff.shape[1], self.owned[1] - self.owned[0]
+        mean = np.empty((A, m), dtype=np.float32)
+        sd = np.empty((A, m), dtype=np.float32) if want_sd else None
+        fp = ctypes.POINTER(ctypes.c_float)
+        check(self._L.phmrf_ancestral(self._h, float(beta), int(estimate_type), self.WEIGHTINGS.index(weighting), int(A),
+                                      ptr_d(aff), ptr_d(cv), mean.ctypes.data_as(fp), sd.ctypes.data_as(fp) if want_sd else None))
+        return mean, sd
+
     def posterior_stats_dev(self, beta, estimate_type, out_dev_ptr):
         check(self._L.phmrf_posterior_stats_dev(self._h, float(beta), int(estimate_type), ctypes.c_void_p(out_dev_ptr)))
 

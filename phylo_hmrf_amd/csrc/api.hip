@@ -589,6 +589,7 @@ int phmrf_block_destroy(phmrf_block_t b) {
   dev_free(b->emis_params);
   dev_free(b->posteriors);
   dev_free(b->summary);
+  dev_free(b->anc);
   for (int r = 0; r < 2; ++r) {
     dev_free(b->pin_save[r]);
     dev_free(b->pin_label[r]);
@@ -1382,11 +1383,55 @@ int phmrf_posterior_summary(phmrf_block_t b, double beta, int estimate_type, flo
   float* d_conf = reinterpret_cast<float*>(b->summary);
   float* d_ent = d_conf + b->n;
   uint8_t* d_top = reinterpret_cast<uint8_t*>(d_ent + b->n);
+  tic(b, KC_POSTERIOR);
   PHMRF_TRY(launch_posterior_summary(b, (float)beta, estimate_type, d_conf, d_top, entropy_or_null ? d_ent : nullptr));
+  toc(b, KC_POSTERIOR, 1);
   PHMRF_HIP(hipMemcpyAsync(conf, d_conf, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, b->stream));
   PHMRF_HIP(hipMemcpyAsync(top, d_top, (size_t)m, hipMemcpyDeviceToHost, b->stream));
   if (entropy_or_null)
     PHMRF_HIP(hipMemcpyAsync(entropy_or_null, d_ent, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+  PHMRF_HIP(hipStreamSynchronize(b->stream));
+  return PHMRF_OK;
+}
+
+// posterior-weighted (weighting 0) or called-state (1) affine maps of the observations over the owned rows: the tables go
+// to the device as f32 [K][A][S+2] = c | g | v, the planes come back with one download each
+int phmrf_ancestral(phmrf_block_t b, double beta, int estimate_type, int weighting, int A, const double* affine,
+                    const double* cond_var, float* mean_out, float* sd_out_or_null) {
+  PHMRF_CHECK(b && affine && cond_var && mean_out, PHMRF_ERR_INVALID, "NULL argument");
+  PHMRF_CHECK(weighting == 0 || weighting == 1, PHMRF_ERR_INVALID, "weighting must be 0 (posterior) or 1 (called)");
+  PHMRF_CHECK(A >= 1 && A <= 16, PHMRF_ERR_UNSUPPORTED, "ancestral: A must be in [1,16]");
+  PHMRF_CHECK(b->S <= 8, PHMRF_ERR_UNSUPPORTED, "ancestral: S must be in [1,8]");
+  const int K = b->K, S = b->S, TS = S + 2;
+  std::vector<float> tab((size_t)K * A * TS);
+  for (int ka = 0; ka < K * A; ++ka) {
+    for (int s = 0; s <= S; ++s) tab[(size_t)ka * TS + s] = (float)affine[(size_t)ka * (S + 1) + s];
+    tab[(size_t)ka * TS + S + 1] = (float)cond_var[ka];
+    PHMRF_CHECK(cond_var[ka] >= 0.0, PHMRF_ERR_INVALID, "cond_var must be finite and >= 0");
+  }
+  for (float v : tab) PHMRF_CHECK(std::isfinite(v), PHMRF_ERR_INVALID, "the tables must be finite (as float32)");
+  PHMRF_CHECK(b->has_X, PHMRF_ERR_STATE, "observations not set");
+  PHMRF_CHECK(b->has_labels, PHMRF_ERR_STATE, "labels not set (phmrf_block_set_labels or a solve)");
+  if (weighting == 0) PHMRF_TRY(check_solvable(b));
+  const int64_t n_first = b->own1 >= 0 ? b->own0 : 0, n_last = b->own1 >= 0 ? b->own1 : b->n;
+  const int64_t m = n_last - n_first;
+  if (m <= 0) return PHMRF_OK;
+  const size_t need = tab.size() + (size_t)2 * A * m;
+  if (b->anc_floats < need) {
+    dev_free(b->anc);
+    b->anc_floats = 0;
+    PHMRF_TRY(dev_alloc(&b->anc, need));
+    b->anc_floats = need;
+  }
+  float* d_mean = b->anc + tab.size();
+  float* d_sd = d_mean + (size_t)A * m;
+  PHMRF_TRY(upload(b->anc, tab.data(), tab.size() * sizeof(float), b->stream));
+  tic(b, KC_POSTERIOR);
+  PHMRF_TRY(launch_ancestral(b, (float)beta, estimate_type, weighting, A, b->anc, d_mean, sd_out_or_null ? d_sd : nullptr));
+  toc(b, KC_POSTERIOR, 1);
+  PHMRF_HIP(hipMemcpyAsync(mean_out, d_mean, (size_t)A * m * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+  if (sd_out_or_null)
+    PHMRF_HIP(hipMemcpyAsync(sd_out_or_null, d_sd, (size_t)A * m * sizeof(float), hipMemcpyDeviceToHost, b->stream));
   PHMRF_HIP(hipStreamSynchronize(b->stream));
   return PHMRF_OK;
 }

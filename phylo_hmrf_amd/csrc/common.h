@@ -174,6 +174,8 @@ struct phmrf_block {
   float* emis_params = nullptr;             // device packed emission parameters
   float* posteriors = nullptr;              // device [n, K], allocated on demand
   char* summary = nullptr;                  // device [n] conf f32 | [n] entropy f32 | [n] top u8 (phmrf_posterior_summary), on demand
+  float* anc = nullptr;                     // device: tables [K][A][S+2] | mean planes [A][owned] | sd planes (phmrf_ancestral), on demand
+  size_t anc_floats = 0;                    //   ... its size
   double* accum = nullptr;                  // device small f64 accumulator area
   double* accum_host = nullptr;             // pinned mirror
   unsigned long long* counters = nullptr;   // device [N_COUNTERS]: the counter bank (slots: above)
@@ -341,6 +343,8 @@ int launch_energy_delta(const phmrf_block* b, double* accum_at = nullptr);   // 
 int launch_posterior_stats(const phmrf_block* b, float beta, int estimate_type, bool write_posteriors);
 int launch_posterior_summary(const phmrf_block* b, float beta, int estimate_type, float* conf, uint8_t* top,
                              float* entropy);   // owned nodes: conf, top, entropy (NULL: skipped) at i - own0
+int launch_ancestral(const phmrf_block* b, float beta, int estimate_type, int weighting, int A, const float* tab, float* mean_out,
+                     float* sd_out);    // tab [K][A][S+2] = c | g[S] | v; planes [A][owned]; sd_out NULL: skipped
 int launch_chain_colour(const phmrf_block* b, float beta, int family, int colour, int phase);
 int launch_component_pass(phmrf_block* b, float beta);
 int launch_component_prepare(phmrf_block* b);

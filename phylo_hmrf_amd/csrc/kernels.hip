@@ -867,6 +867,70 @@ int launch_posterior_s(const phmrf_block* b, float beta, int estimate_type, bool
   return PHMRF_OK;
 }
 
+// Phase 1 of the per-node posterior kernels below: the neighbour-label histogram h[k] of node i in its own LDS row (absent
+// neighbours skipped; an isolated node gets onehot(l_i), :421-423, as in posterior_kernel).
+template <bool GRID>
+__device__ __forceinline__ void label_histogram(float* row, int64_t i, int li, int K, int D, const int32_t* __restrict__ nbr,
+                                                const float* __restrict__ wgt, const uint8_t* __restrict__ labels, int use_w,
+                                                int gH, int gW, int gdiag, const float4* __restrict__ fwd_w) {
+  for (int k = 0; k < K; ++k) row[k] = 0.f;
+  int deg = 0;
+  if (GRID) {
+    int gi, gj;
+    grid_coords(i, gW, gdiag, &gi, &gj);
+    int64_t cc[8];
+    float ww[8];
+    grid_gather_neighbours(i, gi, gj, gH, gW, gdiag, fwd_w, cc, ww);      // (an absent neighbour is the node itself)
+    int ll[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) ll[t] = labels[cc[t]];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      if (cc[t] != i) {
+        row[ll[t]] += use_w ? ww[t] : 1.f;
+        ++deg;
+      }
+    }
+  } else if (D == 8) {
+    const int32_t* nb = nbr + i * D;
+    const float* wg = wgt + i * D;
+    const int4 c0 = *reinterpret_cast<const int4*>(nb), c1 = *reinterpret_cast<const int4*>(nb + 4);
+    const float4 w0 = *reinterpret_cast<const float4*>(wg), w1 = *reinterpret_cast<const float4*>(wg + 4);
+    const int cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+    const float ww[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+    int ll[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) ll[t] = labels[cc[t] >= 0 ? (int64_t)cc[t] : i];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      if (cc[t] >= 0) {
+        row[ll[t]] += use_w ? ww[t] : 1.f;
+        ++deg;
+      }
+    }
+  } else {
+    const int32_t* nb = nbr + i * D;
+    const float* wg = wgt + i * D;
+    for (int j = 0; j < D; j += 4) {
+      const int4 c = *reinterpret_cast<const int4*>(nb + j);
+      const float4 wv = *reinterpret_cast<const float4*>(wg + j);
+      const int cc[4] = {c.x, c.y, c.z, c.w};
+      const float ww[4] = {wv.x, wv.y, wv.z, wv.w};
+      int ll[4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) ll[t] = labels[cc[t] >= 0 ? (int64_t)cc[t] : i];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        if (cc[t] >= 0) {
+          row[ll[t]] += use_w ? ww[t] : 1.f;
+          ++deg;
+        }
+      }
+    }
+  }
+  if (!deg) row[li] = 1.f;
+}
+
 // Per-node summary of the same conditional posterior as posterior_kernel, without statistics: conf = post[l_i] (f32),
 // top = argmax_k post (u8, lowest k on ties), optionally entropy = -sum_k post log post (f32, nats).  Outputs are indexed
 // by owned node, i - n_first.  The histogram, the tile load and the soft-max are posterior_kernel's, step for step, so
@@ -891,62 +955,7 @@ __global__ __launch_bounds__(256) void posterior_summary_kernel(const float* __r
     // phase 1: neighbour-label histogram h[k] in the node's own LDS row (absent neighbours skipped, isolated: onehot(l_i))
     if (live) {
       li = labels[i];
-      for (int k = 0; k < K; ++k) row[k] = 0.f;
-      int deg = 0;
-      if (GRID) {
-        int gi, gj;
-        grid_coords(i, gW, gdiag, &gi, &gj);
-        int64_t cc[8];
-        float ww[8];
-        grid_gather_neighbours(i, gi, gj, gH, gW, gdiag, fwd_w, cc, ww);      // (an absent neighbour is the node itself)
-        int ll[8];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) ll[t] = labels[cc[t]];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-          if (cc[t] != i) {
-            row[ll[t]] += use_w ? ww[t] : 1.f;
-            ++deg;
-          }
-        }
-      } else if (D == 8) {
-        const int32_t* nb = nbr + i * D;
-        const float* wg = wgt + i * D;
-        const int4 c0 = *reinterpret_cast<const int4*>(nb), c1 = *reinterpret_cast<const int4*>(nb + 4);
-        const float4 w0 = *reinterpret_cast<const float4*>(wg), w1 = *reinterpret_cast<const float4*>(wg + 4);
-        const int cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-        const float ww[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
-        int ll[8];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) ll[t] = labels[cc[t] >= 0 ? (int64_t)cc[t] : i];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-          if (cc[t] >= 0) {
-            row[ll[t]] += use_w ? ww[t] : 1.f;
-            ++deg;
-          }
-        }
-      } else {
-        const int32_t* nb = nbr + i * D;
-        const float* wg = wgt + i * D;
-        for (int j = 0; j < D; j += 4) {
-          const int4 c = *reinterpret_cast<const int4*>(nb + j);
-          const float4 wv = *reinterpret_cast<const float4*>(wg + j);
-          const int cc[4] = {c.x, c.y, c.z, c.w};
-          const float ww[4] = {wv.x, wv.y, wv.z, wv.w};
-          int ll[4];
-#pragma unroll
-          for (int t = 0; t < 4; ++t) ll[t] = labels[cc[t] >= 0 ? (int64_t)cc[t] : i];
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            if (cc[t] >= 0) {
-              row[ll[t]] += use_w ? ww[t] : 1.f;
-              ++deg;
-            }
-          }
-        }
-      }
-      if (!deg) row[li] = 1.f;     // isolated (:421-423), as posterior_kernel
+      label_histogram<GRID>(row, i, li, K, D, nbr, wgt, labels, use_w, gH, gW, gdiag, fwd_w);
     }
     __syncthreads();
     // phase 2: tile = logprob + beta*h (the soft-max below is shift-invariant: -beta*Wtot is absorbed by the max)
@@ -1003,6 +1012,186 @@ int launch_posterior_summary(const phmrf_block* b, float beta, int estimate_type
 #undef PHMRF_LAUNCH_SUM
   PHMRF_HIP(hipGetLastError());
   return PHMRF_OK;
+}
+
+// -------------------------------------------------------------------------------------------------
+// Posterior-weighted affine maps of the observations (phmrf_ancestral; DESIGN.md section 7: ancestral contact maps).
+// tab[k][a] = c | g[0..S) | v: mu_ka(x) = c + g . x (an fmaf chain over s), v the conditional variance.  Per owned node
+//   mean_a = sum_k p_k mu_ka(x),   sd_a^2 = sum_k p_k (v_ka + (mu_ka(x) - mean_a)^2)     (never E[z^2] - mean^2)
+// with p_k = row[k] * inv of posterior_summary_kernel's soft-max, step for step, accumulated over k with fmaf.  Outputs
+// are ancestor-major planes [A][m], m = n - n_first owned nodes: every store is coalesced.  The ancestors are taken
+// ANC_CHUNK at a time (accumulators in registers); sd needs the chunk's means first, so mu is formed again in a second
+// pass over k rather than kept (K * ANC_CHUNK registers).  The tables are read from global memory at wave-uniform
+// addresses -- scalar loads, as emission_kernel reads its parameters -- so LDS holds the [TB][Kp] tile only and the
+// kernel keeps the summary kernel's occupancy (40 KB of tables at K = 64, S = 8, A = 16 beside a 33 KB tile would leave two
+// workgroups per CU).  No atomics: a node's outputs depend on its own inputs only.
+// -------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int ANC_CHUNK = 4;
+
+template <int S>
+__device__ __forceinline__ void load_observation(const float* __restrict__ X, int64_t i, float (&x)[S]) {
+  if (S % 4 == 0) {
+#pragma unroll
+    for (int s = 0; s < S; s += 4) {
+      const float4 t = *reinterpret_cast<const float4*>(X + i * S + s);
+      x[s] = t.x; x[s + 1] = t.y; x[s + 2] = t.z; x[s + 3] = t.w;
+    }
+  } else {
+#pragma unroll
+    for (int s = 0; s < S; ++s) x[s] = X[i * S + s];
+  }
+}
+
+template <int S>
+__device__ __forceinline__ float affine_map(const float* __restrict__ t, const float (&x)[S]) {
+  float mu = t[0];
+#pragma unroll
+  for (int s = 0; s < S; ++s) mu = fmaf(t[1 + s], x[s], mu);
+  return mu;
+}
+
+template <int S, int VEC, bool GRID>
+__global__ __launch_bounds__(256) void ancestral_kernel(const float* __restrict__ X, const float* __restrict__ logprob, int64_t n,
+                                                        int K, int Kp, int D, const int32_t* __restrict__ nbr,
+                                                        const float* __restrict__ wgt, const uint8_t* __restrict__ labels,
+                                                        float beta, int use_w, int gH, int gW, int gdiag,
+                                                        const float4* __restrict__ fwd_w, int64_t n_first, int A,
+                                                        const float* __restrict__ tab, float* __restrict__ mean_out,
+                                                        float* __restrict__ sd_out) {
+  extern __shared__ float lds[];
+  constexpr int TS = S + 2;
+  const int TB = blockDim.x;
+  const int64_t m = n - n_first;
+  float* tile = lds;            // [TB][Kp]
+  for (int64_t base = n_first + (int64_t)blockIdx.x * TB; base < n; base += (int64_t)gridDim.x * TB) {
+    const int64_t rem = n - base;
+    const int rows = rem < TB ? (int)rem : TB;
+    const int64_t i = base + threadIdx.x;
+    const bool live = (int)threadIdx.x < rows;
+    float* row = tile + threadIdx.x * Kp;
+    // phases 1 to 3 of posterior_summary_kernel: histogram, tile = logprob + beta*h, soft-max (max, exp, sum in k order)
+    if (live) label_histogram<GRID>(row, i, labels[i], K, D, nbr, wgt, labels, use_w, gH, gW, gdiag, fwd_w);
+    __syncthreads();
+    rows_to_tile<VEC, true>(logprob, nullptr, base, rows, K, Kp, tile, 1.f, beta);
+    __syncthreads();
+    if (live) {
+      float mx = -3.0e38f;
+      for (int k = 0; k < K; ++k) mx = fmaxf(mx, row[k]);
+      float s1 = 0.f;
+      for (int k = 0; k < K; ++k) {
+        const float e = __expf(row[k] - mx);
+        row[k] = e;
+        s1 += e;
+      }
+      const float inv = 1.f / s1;
+      float x[S];
+      load_observation<S>(X, i, x);
+      const int64_t o = i - n_first;
+      // phase 4: the maps, ANC_CHUNK ancestors at a time (k, a0, q are wave-uniform: so are the table addresses)
+      for (int a0 = 0; a0 < A; a0 += ANC_CHUNK) {
+        const int ac = A - a0 < ANC_CHUNK ? A - a0 : ANC_CHUNK;
+        float mean[ANC_CHUNK], var[ANC_CHUNK];
+#pragma unroll
+        for (int q = 0; q < ANC_CHUNK; ++q) mean[q] = var[q] = 0.f;
+        for (int k = 0; k < K; ++k) {
+          const float p = row[k] * inv;
+          const float* t = tab + ((size_t)k * A + a0) * TS;
+#pragma unroll
+          for (int q = 0; q < ANC_CHUNK; ++q)
+            if (q < ac) mean[q] = fmaf(p, affine_map<S>(t + q * TS, x), mean[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < ANC_CHUNK; ++q)
+          if (q < ac) mean_out[(int64_t)(a0 + q) * m + o] = mean[q];
+        if (sd_out) {
+          for (int k = 0; k < K; ++k) {
+            const float p = row[k] * inv;
+            const float* t = tab + ((size_t)k * A + a0) * TS;
+#pragma unroll
+            for (int q = 0; q < ANC_CHUNK; ++q)
+              if (q < ac) {
+                const float d = affine_map<S>(t + q * TS, x) - mean[q];
+                var[q] = fmaf(p, fmaf(d, d, t[q * TS + S + 1]), var[q]);
+              }
+          }
+#pragma unroll
+          for (int q = 0; q < ANC_CHUNK; ++q)
+            if (q < ac) sd_out[(int64_t)(a0 + q) * m + o] = sqrtf(var[q]);
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// `called` weighting: the called state's own map, mean_a = mu_{l_i,a}(x_i), sd_a = sqrt(v_{l_i,a}): no histogram, no tile,
+// no soft-max (the table row is a per-lane gather from 40 KB at most: cache hits)
+template <int S>
+__global__ __launch_bounds__(256) void ancestral_called_kernel(const float* __restrict__ X, int64_t n,
+                                                               const uint8_t* __restrict__ labels, int64_t n_first, int A,
+                                                               const float* __restrict__ tab, float* __restrict__ mean_out,
+                                                               float* __restrict__ sd_out) {
+  constexpr int TS = S + 2;
+  const int64_t m = n - n_first;
+  for (int64_t i = n_first + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    float x[S];
+    load_observation<S>(X, i, x);
+    const float* t = tab + (size_t)labels[i] * A * TS;
+    const int64_t o = i - n_first;
+    for (int a = 0; a < A; ++a, t += TS) {
+      mean_out[(int64_t)a * m + o] = affine_map<S>(t, x);
+      if (sd_out) sd_out[(int64_t)a * m + o] = sqrtf(t[S + 1]);
+    }
+  }
+}
+
+// (grid cap: eight 256-thread workgroups per CU are the CU's 32 waves; above 2048 * 256 owned nodes a workgroup takes a
+//  second tile)
+constexpr int ANC_GRID_CAP = 256 * 8;
+
+template <int S>
+int launch_ancestral_s(const phmrf_block* b, float beta, int estimate_type, int weighting, int A, const float* tab, float* mean_out,
+                       float* sd_out) {
+  const int K = b->K, TB = tile_threads(K), Kp = padded_k(K);
+  const int64_t n_first = b->own1 >= 0 ? b->own0 : 0, n_last = b->own1 >= 0 ? b->own1 : b->n;
+  if (n_last <= n_first) return PHMRF_OK;
+  if (weighting == 1) {
+    const int grid = grid_for(n_last - n_first, 256, ANC_GRID_CAP);
+    hipLaunchKernelGGL((ancestral_called_kernel<S>), dim3(grid), dim3(256), 0, b->stream, b->X, n_last, b->labels, n_first, A, tab,
+                       mean_out, sd_out);
+    PHMRF_HIP(hipGetLastError());
+    return PHMRF_OK;
+  }
+  const size_t lds = (size_t)TB * Kp * sizeof(float);
+  const int grid = grid_for(n_last - n_first, TB, ANC_GRID_CAP * (256 / TB));
+  const int use_w = estimate_type == 3 ? 1 : 0;
+  const bool grid_form = b->has_grid && b->grid_complete && b->fwd_w && b->D == 8 && b->num_neighbor == 8;   // as the summary
+#define PHMRF_LAUNCH_ANC(VEC_, G_)                                                                                          \
+  hipLaunchKernelGGL((ancestral_kernel<S, VEC_, G_>), dim3(grid), dim3(TB), lds, b->stream, b->X, b->logprob, n_last, K, Kp, \
+                     b->D, b->nbr, b->wgt, b->labels, beta, use_w, b->H, b->W, b->diagonal, b->fwd_w, n_first, A, tab,       \
+                     mean_out, sd_out)
+  switch (vec_of(K)) {
+    case 4: if (grid_form) PHMRF_LAUNCH_ANC(4, true); else PHMRF_LAUNCH_ANC(4, false); break;
+    case 2: if (grid_form) PHMRF_LAUNCH_ANC(2, true); else PHMRF_LAUNCH_ANC(2, false); break;
+    default: if (grid_form) PHMRF_LAUNCH_ANC(1, true); else PHMRF_LAUNCH_ANC(1, false); break;
+  }
+#undef PHMRF_LAUNCH_ANC
+  PHMRF_HIP(hipGetLastError());
+  return PHMRF_OK;
+}
+
+}  // namespace
+
+int launch_ancestral(const phmrf_block* b, float beta, int estimate_type, int weighting, int A, const float* tab, float* mean_out,
+                     float* sd_out) {
+  switch (b->S) {
+#define PHMRF_CASE(S_) case S_: return launch_ancestral_s<S_>(b, beta, estimate_type, weighting, A, tab, mean_out, sd_out);
+    PHMRF_CASE(1) PHMRF_CASE(2) PHMRF_CASE(3) PHMRF_CASE(4) PHMRF_CASE(5) PHMRF_CASE(6) PHMRF_CASE(7) PHMRF_CASE(8)
+#undef PHMRF_CASE
+  }
+  return fail(PHMRF_ERR_UNSUPPORTED, "ancestral: S must be in [1,8]");
 }
 
 // ---- launchers --------------------------------------------------------------------------------------

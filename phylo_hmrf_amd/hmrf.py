@@ -444,6 +444,11 @@ class phyloHMRF(_BaseGraph):
         from .segment import segment
         return segment(self, want_entropy)
 
+    def ancestral(self, weighting="posterior", want_sd=True):
+        """the contact map of every internal tree node, with its uncertainty, on the labels the device holds (ancestral.py)"""
+        from .ancestral import reconstruct
+        return reconstruct(self, weighting, want_sd)
+
     def save_model(self, path, species=None, **preprocessing):
         """the fitted model as a self-contained .npz (model_io.py)"""
         from .model_io import save_model

@@ -16,7 +16,10 @@ def tree_for(S):
         return TREE4
     if S == 8:
         return TREE8
-    raise ValueError("synthetic trees are defined for S in {4, 8}")
+    if 2 <= S <= 7:
+        # a caterpillar: internal node 2t has the leaf 2t + 1 and the next internal node 2t + 2; the last one has two leaves
+        return [[2 * t, 2 * t + c] for t in range(S - 1) for c in (1, 2)]
+    raise ValueError("synthetic trees are defined for S in [2, 8]")
 
 
 def sample_ou_params(rng, tree, K):

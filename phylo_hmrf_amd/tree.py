@@ -82,6 +82,29 @@ class PhyloTree(object):
             order.append(v)
             stack.extend(children[v])
         self.order = [v for v in order if parent[v] >= 0]
+        # internal nodes (the root included) in node order: the ancestors whose values a fitted model can reconstruct
+        self.internal_nodes = np.array([i for i in range(N) if children[i]], dtype=np.int64)
+        # every pair of nodes: nearest common ancestor (-1: none, two trees of a forest) and the nodes on the path between
+        # the two, the ancestor excluded -- pair_anc / A2 above written for all pairs (joint_moments)
+        up = []
+        for i in range(N):
+            chain, p = [i], parent[i]
+            while p >= 0:
+                chain.append(int(p))
+                p = parent[p]
+            up.append(chain)
+        self.node_anc = np.full((N, N), -1, dtype=np.int64)
+        self.node_path = np.zeros((N, N, N))
+        for i in range(N):
+            si = set(up[i])
+            for j in range(N):
+                common = si & set(up[j])
+                if not common:
+                    continue
+                self.node_anc[i, j] = next(v for v in up[i] if v in common)      # the first common node on the way up
+                for v in up[i] + up[j]:
+                    if v not in common:
+                        self.node_path[i, j, v] = 1.0
 
     # -- parameter slices --------------------------------------------------------------------------
     def split(self, params):
@@ -129,6 +152,38 @@ class PhyloTree(object):
         means[..., self.leaf_col] = mean[..., self.leaf_vec]                              # :1033
         # the reference indexes means by leaf order (values[leaf_vec]); leaf_col is the identity (checked in __init__)
         return means, cov + min_covar * np.eye(S)
+
+    def joint_moments(self, params):
+        """The joint Gaussian of ALL tree nodes under node_moments' recursion X_i = e_i X_parent + (1 - e_i) theta_i + eps_i:
+        params [..., 3B+2] -> (mean [..., N], cov [..., N, N]) with cov[i, j] = var[mrca(i, j)] * prod of e over the nodes on
+        the path between i and j, the mrca excluded (mean_cov's leaf-pair expression for every pair; no min_covar)."""
+        params = np.asarray(params, dtype=np.float64)
+        _, beta, _, _ = self.split(params)
+        shp = beta.shape[:-1]
+        mean, var, _, _ = self.node_moments(params)
+        N = self.node_num
+        beta_full = np.concatenate([np.zeros(shp + (1,)), beta], axis=-1)
+        s1 = np.einsum("ijn,...n->...ij", self.node_path, beta_full)
+        anc = self.node_anc
+        cov = np.where(anc >= 0, var[..., np.maximum(anc, 0)] * np.exp(-s1), 0.0)
+        idx = np.arange(N)
+        cov[..., idx, idx] = var
+        return mean, cov
+
+    def ancestral_tables(self, params, min_covar=1e-3):
+        """Conditioning the internal nodes A (internal_nodes, root included) on the leaves L (feature order) per state, with
+        min_covar as the model's observation noise -- the emission's covariance C_LL + min_covar I as it stands:
+          G = C_AL (C_LL + min_covar I)^-1,  E[z_A | x] = c + G x with c = m_A - G m_L,  Var[z_A | x] = diag(C_AA - G C_LA).
+        params [K, 3B+2] -> (affine [K, A, S+1]: c, then the row of G;  cond_var [K, A], clipped at 0)"""
+        mean, cov = self.joint_moments(params)
+        A, L = self.internal_nodes, self.leaf_vec
+        S = self.n_features
+        C_LL = cov[..., L[:, None], L[None, :]] + min_covar * np.eye(S)
+        C_LA = cov[..., L[:, None], A[None, :]]
+        G = np.swapaxes(np.linalg.solve(C_LL, C_LA), -1, -2)                  # (C_LL is symmetric)
+        c = mean[..., A] - np.einsum("...as,...s->...a", G, mean[..., L])
+        cond_var = cov[..., A, A] - np.einsum("...as,...sa->...a", G, C_LA)
+        return np.concatenate([c[..., None], G], axis=-1), np.maximum(cond_var, 0.0)
 
 
 def load_tree_files(data_path):
