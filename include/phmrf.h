@@ -359,6 +359,48 @@ PHMRF_API int phmrf_ancestral(phmrf_block_t b, double beta, int estimate_type, i
 PHMRF_API int phmrf_smooth_labels(const uint8_t* labels_dev, uint8_t* out_dev, int H, int W, int diagonal, int K, int window,
                                   int64_t max_area, int n_iter, int64_t* counts_host, void* hip_stream);
 
+/* ---- comparing two state maps ---------------------------------------------------------------------- */
+/* Two state maps of ONE region, no block (no ABI bump: the calls only add entry points).  u8 labels
+ * on the device in the node order of phmrf_smooth_labels.  Both calls are queued on hip_stream (NULL: the null stream),
+ * return when done and use integers only: the results are the same from run to run.
+ *
+ * phmrf_label_contingency: counts_host[a * KB + b] (host int64 [KA * KB]) = the number of STORED nodes with state a in
+ * a_dev and b in b_dev (u8 [n] each; a diagonal block's bin pairs count once).  The maps are read four nodes per lane
+ * where both can be 4-byte aligned at the same node, byte-wise otherwise.
+ * PHMRF_ERR_INVALID for a NULL pointer, n < 0, K < 1 or a label >= K in either map (nothing written);
+ * PHMRF_ERR_UNSUPPORTED for K > 64 or n >= 2^31 - 64. */
+PHMRF_API int phmrf_label_contingency(const uint8_t* a_dev, const uint8_t* b_dev, int64_t n, int KA, int KB,
+                                      int64_t* counts_host /* [KA*KB], row a, column b */, void* hip_stream);
+
+/* phmrf_diff_domains: where the two maps differ, and the connected domains of the difference.  Per stored node, with
+ * b' = map_b[b] (map_b_host_or_null: host u8 [KB], values < 64; NULL: b' = b):
+ *   diff = 0 where a == b', 2 where they differ and the node counts, 1 where they differ and it does not.
+ * A node counts when both confidences (float32 [n], device; both given or neither) are >= min_conf; with no confidences or
+ * min_conf <= 0 every differing node counts.  diff_out_dev_or_null: u8 [n], device.
+ * The DOMAINS are the 8-connected components of diff == 2 on the region's full (symmetric) matrix, with the smoothing's
+ * conventions: a diagonal block's component with a node at j - i <= 1 is its own mirror and has area 2 nodes - diagonal
+ * nodes; any other component has a twin of equal area and is listed once.  Domains with area >= min_area are listed in
+ * ascending order of their root, the smallest stored node id.  *n_domains is their number; the first
+ * min(*n_domains, capacity) get a row of PHMRF_DOMAIN_COLS int64 in table_host [capacity * 12]:
+ *   0 root   1-4 i0 i1 j0 j1, the inclusive bounding box of the domain's STORED nodes   5 stored nodes   6 area
+ *   7, 8 the domain's most frequent state in A and in mapped B (the lowest state on ties)
+ *   9, 10 the sums over the domain's nodes of floor(conf_a 2^24) and floor(conf_b 2^24) (exact; 0 without confidences)   11 0
+ * band_counts_host_or_null: host int64 [PHMRF_DIFF_BANDS * 3]: per band of the distance d = |dist0 + j - i| (band 0:
+ * d == 0; band t >= 1: 2^(t-1) <= d < 2^t; dist0 = start_bin2 - start_bin1, 0 for a diagonal block) the nodes, the nodes
+ * with diff >= 1 and the nodes with diff == 2.
+ * Errors as phmrf_smooth_labels (a label >= K, a non-square diagonal block: PHMRF_ERR_INVALID, nothing written; K > 64 or
+ * n >= 2^31 - 64: PHMRF_ERR_UNSUPPORTED), and PHMRF_ERR_INVALID for capacity < 0, min_area < 1, a NULL table with
+ * capacity > 0, one confidence without the other, a confidence that is not a finite number in [0, 1], a map value >= 64,
+ * or a distance of 2^31 or more. */
+#define PHMRF_DIFF_BANDS 32
+#define PHMRF_DOMAIN_COLS 12
+PHMRF_API int phmrf_diff_domains(const uint8_t* a_dev, const uint8_t* b_dev, const uint8_t* map_b_host_or_null /* [KB] */,
+                                 const float* conf_a_dev_or_null, const float* conf_b_dev_or_null, int H, int W, int diagonal,
+                                 int64_t dist0, int KA, int KB, float min_conf, int64_t min_area,
+                                 uint8_t* diff_out_dev_or_null /* [n] */, int64_t capacity,
+                                 int64_t* table_host /* [capacity*12] */, int64_t* n_domains,
+                                 int64_t* band_counts_host_or_null /* [32*3] */, void* hip_stream);
+
 /* ---- pre-processing filters ----------------------------------------------------------------------- */
 /* ABI 127: the raw loader's smoothing filters (phylo_hmrf_amd/preprocess.py) on ONE H x W plane of a
  * contact map, no block: row-major device buffers of H W pixels, pixel units throughout (sigmas, window and radius count

@@ -101,6 +101,18 @@ def parse_args(argv=None):
     parser.add_option("--smooth_iter", default="1", help="--postprocess: number of smoothing passes")
     parser.add_option("--filter_device", default="0", help="1: run the loader's smoothing filter (--filter_mode) on the GPU; "
                       "0 (default): on the host.  Not with --reload 1, --synthetic or --postprocess, which filter nothing")
+    parser.add_option("--compare", default="", help="skip loading data and fitting: compare the states of this .mat with those "
+                      "of --compare_with on the same regions (contingency table, agreement, ARI, NMI, differential domains); "
+                      "writes compare_<A>__<B>.mat and compare_domains_<A>__<B>.txt in genome coordinates (--resolution) under "
+                      "--output")
+    parser.add_option("--compare_with", default="", help="--compare: the second .mat")
+    parser.add_option("--compare_field", default="state_vec", help="--compare: state_vec or state_vec_smooth")
+    parser.add_option("--compare_match", default="0", help="--compare: 1 = renumber the second map's states to the first's by "
+                      "the best one-to-one assignment first (two fits of their own)")
+    parser.add_option("--compare_min_conf", default="0", help="--compare: a differing bin pair counts only when both files' conf "
+                      "reach this (0: every differing bin pair counts)")
+    parser.add_option("--compare_area", default="-1", help="--compare: smallest area of a listed domain (-1: one more than the "
+                      "smoothing's small-region area, 81, or 26 for a region less than 100 bins high)")
     parser.add_option("-h", "--help", action="help")
     opts, _ = parser.parse_args(argv)
     return opts
@@ -228,13 +240,33 @@ def check_ancestral(ancestral, segment, postprocess):
                          "its segmentation")
 
 
+def check_compare(compare, compare_with, compare_field, compare_match, segment, postprocess, ancestral, save_model,
+                  filter_device):
+    """--compare A.mat --compare_with B.mat reads two finished state maps: it goes with nothing that loads data or fits"""
+    if not compare and not compare_with:
+        return
+    if not compare or not compare_with:
+        raise SystemExit("--compare and --compare_with go together: the two .mat files to compare")
+    for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--ancestral", ancestral),
+                        ("--save_model", save_model), ("--filter_device 1", str(filter_device) == "1")):
+        if value:
+            raise SystemExit("--compare cannot be combined with %s: it loads no data and fits nothing" % name)
+    if compare_field not in ("state_vec", "state_vec_smooth"):
+        raise SystemExit("--compare_field must be state_vec or state_vec_smooth, not %r" % (compare_field,))
+    if str(compare_match) not in ("0", "1"):
+        raise SystemExit("--compare_match must be 0 or 1")
+
+
 def run(num_states, chromvec, root_path, multiple, species_name, sort_states, run_id1, cons_param, method_mode,
         initial_mode, initial_weight, initial_weight1, initial_magnitude, position1, position2, filter_sigma, beta,
         beta1, num_neighbor, filter_mode, conv_threshold, estimate_type, simu_version, annotation, reload_mode,
         diagonal_type, m_iter, resolution, quantile, ref_species, output_path, synthetic="0", seed="", quiet="0",
         init_method="minibatch", warm_start="best", checkpoint="", checkpoint_every="1", resume="", energy_tol_ppb="10000",
         save_model="", segment="", postprocess="", smooth_window="5", smooth_area="-1", smooth_iter="1",
-        filter_device="0", ancestral=""):
+        filter_device="0", ancestral="", compare="", compare_with="", compare_field="state_vec", compare_match="0",
+        compare_min_conf="0", compare_area="-1"):
+    check_compare(compare, compare_with, compare_field, compare_match, segment, postprocess, ancestral, save_model,
+                  filter_device)
     check_ancestral(ancestral, segment, postprocess)
     filter_device = int(filter_device)
     if filter_device not in (0, 1):
@@ -242,6 +274,14 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
     if filter_device and (int(reload_mode) == 1 or int(synthetic) > 0 or postprocess):
         raise SystemExit("--filter_device 1 runs the raw loader's filter on the GPU: it cannot be combined with --reload 1, "
                          "--synthetic or --postprocess, where nothing is filtered")
+    if compare:
+        from phylo_hmrf_amd.compare import compare_files
+        area = int(compare_area)
+        out = compare_files(compare, compare_with, str(output_path), int(resolution), field=compare_field,
+                            match=bool(int(compare_match)), min_conf=float(compare_min_conf),
+                            min_area=None if area == -1 else area)
+        print("comparison written: %s" % out)
+        return out
     if postprocess:
         from phylo_hmrf_amd.smooth import postprocess_file
         area = int(smooth_area)
@@ -412,4 +452,6 @@ if __name__ == "__main__":
         checkpoint=opts.checkpoint, checkpoint_every=opts.checkpoint_every, resume=opts.resume,
         energy_tol_ppb=opts.energy_tol_ppb, save_model=opts.save_model, segment=opts.segment,
         postprocess=opts.postprocess, smooth_window=opts.smooth_window, smooth_area=opts.smooth_area,
-        smooth_iter=opts.smooth_iter, filter_device=opts.filter_device, ancestral=opts.ancestral)
+        smooth_iter=opts.smooth_iter, filter_device=opts.filter_device, ancestral=opts.ancestral,
+        compare=opts.compare, compare_with=opts.compare_with, compare_field=opts.compare_field,
+        compare_match=opts.compare_match, compare_min_conf=opts.compare_min_conf, compare_area=opts.compare_area)

@@ -1,0 +1,60 @@
+// What the post-processing's kernel files share (smooth.hip, compare.hip): the capped grid, the wave helpers of their integer
+// accumulations -- one atomic per RUN of equal destination among consecutive lanes, because state maps are piecewise
+// constant -- and the full-matrix area of a grid component.
+#pragma once
+
+#include "common.h"
+
+namespace phmrf {
+
+inline int grid_of(int64_t n, int tb = 256, int cap = 256 * 16) {
+  int64_t g = (n + tb - 1) / tb;
+  if (g > cap) g = cap;
+  return g < 1 ? 1 : (int)g;
+}
+
+__device__ __forceinline__ unsigned long long lanes_at_or_below(int lane) {
+  return lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
+}
+
+__device__ __forceinline__ void wave_add(unsigned long long* dst, unsigned long long x) {   // one atomic per wave
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+  if ((threadIdx.x & 63) == 0 && x) atomicAdd(dst, x);
+}
+
+// dst[key] += x, one atomic per run of equal key among consecutive lanes (key < 0: the lane adds nothing).  Every lane of
+// the wave must call it.  Inclusive prefix sum, each run's last lane adds the run's part.
+template <typename T>
+__device__ __forceinline__ void wave_run_add(T* dst, int key, T x) {
+  const int lane = threadIdx.x & 63;
+  const int key_prev = __shfl_up(key, 1, 64);
+  const bool head = lane == 0 || key_prev != key;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const T t = __shfl_up(x, off, 64);
+    if (lane >= off) x += t;
+  }
+  const unsigned long long heads = __ballot(head);
+  const int h = 63 - __clzll((long long)(heads & lanes_at_or_below(lane)));
+  const T before = __shfl(x, h > 0 ? h - 1 : 0, 64);
+  const bool next_head = lane == 63 || ((heads >> (lane + 1)) & 1ull);
+  if (key >= 0 && next_head) atomicAdd(dst + key, x - (h > 0 ? before : (T)0));
+}
+
+// the area on the full matrix of the component with root v, from acc[v] = (weight << 32) | nodes (weight: 1 per diagonal
+// node, 2 per other node) and mirror[v] = a node has j - i <= 1: a diagonal block's component that is its own mirror counts
+// its off-diagonal nodes twice, any other component its stored nodes
+__device__ __forceinline__ long long component_area(int64_t v, int diagonal, const unsigned long long* __restrict__ acc,
+                                                    const uint8_t* __restrict__ mirror) {
+  const unsigned long long a = acc[v];
+  return (diagonal && mirror[v]) ? (long long)(a >> 32) : (long long)(a & 0xffffffffull);
+}
+
+template <typename T>
+int alloc(T** p, size_t count) {
+  PHMRF_HIP(hipMalloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(T)));
+  return PHMRF_OK;
+}
+
+}  // namespace phmrf

@@ -21,20 +21,10 @@
 //
 // All counts are integers: the result does not depend on the order in which the atomics land.
 
-#include "common.h"
+#include "runs.h"
 
 namespace phmrf {
 namespace {
-
-inline int grid_of(int64_t n, int tb = 256, int cap = 256 * 16) {
-  int64_t g = (n + tb - 1) / tb;
-  if (g > cap) g = cap;
-  return g < 1 ? 1 : (int)g;
-}
-
-__device__ __forceinline__ unsigned long long lanes_at_or_below(int lane) {
-  return lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
-}
 
 // *bad = 1 if any label >= K
 __global__ __launch_bounds__(256) void smooth_check_kernel(const uint8_t* __restrict__ labels, int64_t n, int K,
@@ -61,34 +51,14 @@ __global__ __launch_bounds__(256) void smooth_area_kernel(const int32_t* __restr
       x = ((unsigned long long)(diagonal && i == j ? 1 : 2) << 32) | 1ull;
       if (diagonal && j - i <= 1) mirror[key] = 1;
     }
-    // runs of equal root among consecutive lanes: inclusive prefix sum, each run's last lane adds the run's part
-    const int key_prev = __shfl_up(key, 1, 64);
-    const bool head = lane == 0 || key_prev != key;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const unsigned long long t = __shfl_up(x, off, 64);
-      if (lane >= off) x += t;
-    }
-    const unsigned long long heads = __ballot(head);
-    const int h = 63 - __clzll((long long)(heads & lanes_at_or_below(lane)));
-    const unsigned long long before = __shfl(x, h > 0 ? h - 1 : 0, 64);
-    const bool next_head = lane == 63 || ((heads >> (lane + 1)) & 1ull);
-    if (key >= 0 && next_head) atomicAdd(acc + key, x - (h > 0 ? before : 0ull));
+    wave_run_add(acc, key, x);                 // one packed atomic per run of equal root among consecutive lanes
   }
-}
-
-__device__ __forceinline__ void wave_add(unsigned long long* dst, unsigned long long x) {   // one atomic per wave
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-  if ((threadIdx.x & 63) == 0 && x) atomicAdd(dst, x);
 }
 
 __device__ __forceinline__ bool small_root(const int32_t* __restrict__ comp, int64_t v, int diagonal,
                                            const unsigned long long* __restrict__ acc, const uint8_t* __restrict__ mirror,
                                            long long max_area) {
-  const unsigned long long a = acc[v];
-  const long long area = (diagonal && mirror[v]) ? (long long)(a >> 32) : (long long)(a & 0xffffffffull);
-  return area <= max_area;
+  return component_area(v, diagonal, acc, mirror) <= max_area;
 }
 
 // cid[root] = compact id of a small component, -1 for a large one (roots only: nothing reads cid elsewhere).  Every
@@ -224,12 +194,6 @@ struct SmoothWork {
       if (p) (void)hipFree(p);
   }
 };
-
-template <typename T>
-int alloc(T** p, size_t count) {
-  PHMRF_HIP(hipMalloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(T)));
-  return PHMRF_OK;
-}
 
 }  // namespace
 }  // namespace phmrf
