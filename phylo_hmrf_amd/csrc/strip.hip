@@ -15,6 +15,7 @@
 // the pass never raises the energy.   (Model: oracle/mrf_moves.strip_fusion.)
 
 #include <cstdlib>
+#include <type_traits>
 #include <utility>
 
 #include "common.h"
@@ -163,6 +164,45 @@ __device__ __forceinline__ void build_table(float* tab, int lane, float c0, floa
   }
 }
 
+// ONE b half of a cell's record (16 floats), for the chunked DP, where a chunk's cells are at most 18 lanes: the cell's own
+// lane builds b = 0 and its xor-32 partner lane, which holds a copy of the record, builds b = 1 -- the two halves share
+// nothing.  `bits` arrives with the half's neighbour bits where b = 0 has them (partner_bits); the sums and their order are
+// build_table's.
+__device__ __forceinline__ void build_half(float4* dst, float cb, float wu, float wlu, float wl, float wld, int bits) {
+  const float lus = bit_masked(wlu, bits, 4), luo = bit_masked(wlu, bits, 5);
+  float cA[2], cAB[2][2];
+#pragma unroll
+  for (int bu = 0; bu < 2; ++bu) cA[bu] = cb + bit_masked(wu, bits, bu);
+#pragma unroll
+  for (int bu = 0; bu < 2; ++bu)
+#pragma unroll
+    for (int bl = 0; bl < 2; ++bl) cAB[bu][bl] = cA[bu] + bit_masked(wl, bits, 8 + bl);
+  const float C0 = bit_masked(wld, bits, 12), C1 = bit_masked(wld, bits, 13);
+#pragma unroll
+  for (int bu = 0; bu < 2; ++bu)
+#pragma unroll
+    for (int bl = 0; bl < 2; ++bl) {
+      const float x0 = cAB[bu][bl] + C0, x1 = cAB[bu][bl] + C1;
+      dst[bu * 2 + bl] = make_float4(x0 + lus, x0 + luo, x1 + lus, x1 + luo);
+    }
+}
+// the record bits as the b = 1 half reads them: every neighbour's pair (b = 1, .) two places down, where b = 0 has its
+// pair, and the left-up pair (self = bit 7, other = bit 6) at bits 4 and 5
+__device__ __forceinline__ int partner_bits(int bits) {
+  return (int)((((unsigned int)bits >> 2) & ~0x30u) | (((unsigned int)bits >> 3) & 0x10u) | (((unsigned int)bits >> 1) & 0x20u));
+}
+// the value of lane ^ 32
+__device__ __forceinline__ int xor32_i32(int v) {
+  auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+  return (int)((wave_lane() & 32) ? r[0] : r[1]);
+}
+__device__ __forceinline__ float xor32_f32(float v) { return __builtin_bit_cast(float, xor32_i32(__builtin_bit_cast(int, v))); }
+// the b = 1 operands of a cell, as its partner lane holds them
+struct HalfRec {
+  float c1, wu, wlu, wl, wld;
+  int bits;
+};
+
 // One cell step of the profile DP.  The profile is kept in ROTATING positions: cell t owns bit (t mod 6) of the state
 // index (= lane id), so stepping to cell t overwrites the bit of cell t-6 (the left-up neighbour, about to leave the
 // profile) and new[s] = base[s] + min over that old bit d of (old[s with bit q := d] + lu[b][d]): the two candidates
@@ -197,6 +237,18 @@ __device__ __forceinline__ void dp_step(float& m, unsigned long long& took, floa
 // one uniform value into one lane of a VGPR as a plain select (v_cmp + v_cndmask, no exec juggling)
 __device__ __forceinline__ void write_lane(unsigned int& dst, unsigned int value, int lane_sel) {
   dst = (wave_lane() == lane_sel) ? value : dst;
+}
+// ... and a wave-uniform 64-bit value (a ballot) into a lane known at compile time of a register pair: one v_writelane_b32
+// per half (the compiler has no builtin for it; the lane is an inline constant, so each reads one scalar register, the
+// value; it ignores exec: callers run with the whole wave).  The compiler does not look into the statement, so the wait
+// states gfx950 wants between the vector compare that wrote the ballot and a vector instruction that reads it as a scalar
+// operand (two) are in it.
+template <int LANE>
+__device__ __forceinline__ void write_lane64_at(unsigned int& dlo, unsigned int& dhi, unsigned long long value) {
+  static_assert(LANE >= 0 && LANE < 64, "lane");
+  asm("s_nop 1\n\tv_writelane_b32 %0, %2, %4\n\tv_writelane_b32 %1, %3, %4"
+      : "+v"(dlo), "+v"(dhi)
+      : "s"((unsigned int)(value & 0xffffffffull)), "s"((unsigned int)(value >> 32)), "n"(LANE));
 }
 
 // One step at a compile-time position: the table addresses are a per-lane register plus an immediate offset.
@@ -764,40 +816,30 @@ constexpr int SLABW = (63 + 2) * SWC;        // floats
 constexpr int SLABL = ((63 + 2) * EH + 3) / 4 * 4;   // label bytes
 constexpr int CH = 18;                       // cells per table chunk: three groups of six DP steps
 constexpr int NBUF = 8;                      // flagged labels buffered before the wave turns to the DP
-// everything strip_cols_kernel keeps in LDS (one wave per workgroup): 9.9 KB
-struct ColsLds {
+// everything strip_cols_kernel keeps in LDS (one wave per workgroup): 9.9 KB with the NBUF entries of the expansions
+template <int NB>
+struct ColsLdsT {
   alignas(16) float tabch[CH * 36];          // DP tables of one chunk (2.6 KB; 36 = TAB)
   alignas(16) float slabw[SLABW];            // the staged rectangle, never overwritten: forward weights ...
-  unsigned long long ubuf[NBUF][SH];         // U of the flagged labels, one word per strip row
-  int abuf[NBUF];                            // ... and which labels they are
+  unsigned long long ubuf[NB][SH];           // U of the flagged labels, one word per strip row
+  int abuf[NB];                              // ... and which labels they are
   unsigned int wk[WORK_SLOTS];
   int nbuf;
   unsigned char slabl[SLABL];                // ... and label bytes of the staged rectangle
 };
+using ColsLds = ColsLdsT<NBUF>;
 
-// ... and of fusion_cols_kernel: the same, plus the proposal byte of every staged cell
+// ... and of fusion_cols_kernel: the same with ONE U entry (the pass has one move per strip), plus the proposal byte of
+// every staged cell: 10,096 B, so that a CU holds as many of its one-wave workgroups as of the expansions'
 struct FusLds {
-  ColsLds c;
+  ColsLdsT<1> c;
   unsigned char slabp[SLABL];
 };
+static_assert(sizeof(FusLds) <= 10240, "fusion_cols_kernel's LDS is to stay within 10 KB");
 
+// the steps of chunk C of pass P; lane T of (dlo, dhi) keeps the decision ballot of step T
 template <int P, int C, int... TT>
 __device__ __forceinline__ void dp_chunk_steps(float& m, unsigned long long& took, int lane, const char* tabc,
-                                               std::integer_sequence<int, TT...>) {
-  (([&] {
-     constexpr int T = C * CH + TT;
-     if constexpr (T < 64) {
-       constexpr int Q = (4 * P + T) % 6;
-       const float2 tv = *reinterpret_cast<const float2*>(tabc + TT * (TAB * 4) + tab_offset<Q>(state_of_lane(lane)));
-       unsigned long long dec;
-       dp_step<Q>(m, took, tv.x, tv.y, &dec);
-     }
-   }()),
-   ...);
-}
-
-template <int P, int C, int... TT>
-__device__ __forceinline__ void dp_chunk_steps_rec(float& m, unsigned long long& took, int lane, const char* tabc,
                                                    unsigned int& dlo, unsigned int& dhi, std::integer_sequence<int, TT...>) {
   (([&] {
      constexpr int T = C * CH + TT;
@@ -806,15 +848,15 @@ __device__ __forceinline__ void dp_chunk_steps_rec(float& m, unsigned long long&
        const float2 tv = *reinterpret_cast<const float2*>(tabc + TT * (TAB * 4) + tab_offset<Q>(state_of_lane(lane)));
        unsigned long long dec;
        dp_step<Q>(m, took, tv.x, tv.y, &dec);
-       write_lane(dlo, (unsigned int)(dec & 0xffffffffull), T);
-       write_lane(dhi, (unsigned int)(dec >> 32), T);
+       write_lane64_at<T>(dlo, dhi, dec);
      }
    }()),
    ...);
 }
 
-// chunk C of pass P: the chunk's cells build their tables (lanes C*18 .. C*18+17 hold their records), then every state
-// walks them.  [t_lo, t_end] is wave-uniform and aligned to chunks.
+// chunk C of pass P: the chunk's cells build their tables (lanes C*18 .. C*18+17 hold their records and build the b = 0
+// halves, their xor-32 partners -- for every chunk lanes outside it -- the b = 1 halves from the copies in `hp`), then
+// every state walks them.  [t_lo, t_end] is wave-uniform and aligned to chunks.
 #ifdef PHMRF_PHASE_DP
 // development build: shader-clock cycles of the DP's sub-phases into the work counters (1 U conversion + unary loads,
 // 2 records, 3 table builds, 4 walks, 5 everything after a move was found)
@@ -828,37 +870,49 @@ __device__ unsigned int* dp_wk_dummy;
 #else
 #define DPH(K_)
 #endif
-template <int P, int C, bool RECORD>
-__device__ __forceinline__ void dp_chunk(float& m, unsigned long long& took, int lane, float* tabch, float c0, float c1,
-                                         float wu, float wlu, float wl, float wld, int bits, int t_lo, int t_end,
+template <int P, int C>
+__device__ __forceinline__ void dp_chunk(float& m, unsigned long long& took, int lane, float* tabch, float c0,
+                                         float wu, float wlu, float wl, float wld, int bits, const HalfRec& hp, int t_lo, int t_end,
                                          unsigned int& dlo, unsigned int& dhi, unsigned int live, unsigned int* dp_wk,
                                          unsigned long long& dp_t0) {
   constexpr int T0 = C * CH, T1 = (T0 + CH - 1 < 63) ? T0 + CH - 1 : 63;
+  static_assert(T1 - T0 < 32, "a chunk's partner lanes (lane ^ 32) lie outside the chunk");
   if (P * 64 + T0 > t_end || P * 64 + T1 < t_lo) return;
   // A chunk none of whose cells, nor the six before it, is in U: every cell it holds is pinned and the profile it starts
   // from is 000000 in every finite state -- walking it would only add the same constant to the one finite state.
   if (!((live >> (P * 4 + C)) & 1u)) return;
-  if (lane >= T0 && lane <= T1) build_table(tabch, lane - T0, c0, c1, wu, wlu, wl, wld, bits);
+  {
+    const int lp = lane ^ 32;
+    const bool own = lane >= T0 && lane <= T1, par = lp >= T0 && lp <= T1;
+    if (own || par) {
+      // (words 0 .. 15 of the cell's record: b = 0, words 16 .. 31: b = 1.  Bank pattern of the ds_write_b128: the lanes of
+      //  one role hold consecutive cells, 36 words apart, and no aligned group of 16 lanes holds both roles, so within a
+      //  group the four-word units 36 i + const are distinct mod 64 (and mod 32 within a group of 8): conflict-free as before)
+      float4* dst = reinterpret_cast<float4*>(tabch + ((own ? lane : lp) - T0) * TAB + (own ? 0 : 16));
+      build_half(dst, own ? c0 : hp.c1, own ? wu : hp.wu, own ? wlu : hp.wlu, own ? wl : hp.wl, own ? wld : hp.wld, own ? bits : hp.bits);
+    }
+  }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   DPH(3)
   const char* tabc = reinterpret_cast<const char*>(tabch);
-  if (RECORD) dp_chunk_steps_rec<P, C>(m, took, lane, tabc, dlo, dhi, std::make_integer_sequence<int, CH>{});
-  else dp_chunk_steps<P, C>(m, took, lane, tabc, std::make_integer_sequence<int, CH>{});
+  dp_chunk_steps<P, C>(m, took, lane, tabc, dlo, dhi, std::make_integer_sequence<int, CH>{});
   __builtin_amdgcn_wave_barrier();
   DPH(4)
 }
 
-template <int P, bool RECORD>
+template <int P>
 __device__ __forceinline__ void dp_pass_chunked(float& m, unsigned long long& took, int lane, float* tabch, float c0, float c1,
                                                 float wu, float wlu, float wl, float wld, int bits, int t_lo, int t_end,
                                                 unsigned int& dlo, unsigned int& dhi, unsigned int live, unsigned int* dp_wk,
                                                 unsigned long long& dp_t0) {
   if (P * 64 > t_end || P * 64 + 63 < t_lo) return;
-  dp_chunk<P, 0, RECORD>(m, took, lane, tabch, c0, c1, wu, wlu, wl, wld, bits, t_lo, t_end, dlo, dhi, live, dp_wk, dp_t0);
-  dp_chunk<P, 1, RECORD>(m, took, lane, tabch, c0, c1, wu, wlu, wl, wld, bits, t_lo, t_end, dlo, dhi, live, dp_wk, dp_t0);
-  dp_chunk<P, 2, RECORD>(m, took, lane, tabch, c0, c1, wu, wlu, wl, wld, bits, t_lo, t_end, dlo, dhi, live, dp_wk, dp_t0);
-  dp_chunk<P, 3, RECORD>(m, took, lane, tabch, c0, c1, wu, wlu, wl, wld, bits, t_lo, t_end, dlo, dhi, live, dp_wk, dp_t0);
+  // every lane's copy of its partner's record, once per pass: one v_permlane32_swap per value
+  const HalfRec hp = {xor32_f32(c1), xor32_f32(wu), xor32_f32(wlu), xor32_f32(wl), xor32_f32(wld), partner_bits(xor32_i32(bits))};
+  dp_chunk<P, 0>(m, took, lane, tabch, c0, wu, wlu, wl, wld, bits, hp, t_lo, t_end, dlo, dhi, live, dp_wk, dp_t0);
+  dp_chunk<P, 1>(m, took, lane, tabch, c0, wu, wlu, wl, wld, bits, hp, t_lo, t_end, dlo, dhi, live, dp_wk, dp_t0);
+  dp_chunk<P, 2>(m, took, lane, tabch, c0, wu, wlu, wl, wld, bits, hp, t_lo, t_end, dlo, dhi, live, dp_wk, dp_t0);
+  dp_chunk<P, 3>(m, took, lane, tabch, c0, wu, wlu, wl, wld, bits, hp, t_lo, t_end, dlo, dhi, live, dp_wk, dp_t0);
 }
 
 // ---- the exact filter on one strip, lane <-> strip column (shared by strip_cols_kernel and fusion_cols_kernel) -------
@@ -1013,7 +1067,8 @@ __device__ PHMRF_DP_INLINE unsigned int dp_flagged(StripGeom g, unsigned int lds
     const global_ptr<uint8_t> labels = as_global(labels_);
     const global_ptr<uint16_t> stamp = as_global(stamp_);
     const global_ptr<uint16_t> mslot = as_global(mslot_);       // this move's memo entry (label alpha's, or the fusion pass's)
-    ColsLds* L = lds_object<ColsLds>(lds);
+    using Lds = std::conditional_t<FUSION, ColsLdsT<1>, ColsLds>;      // (FusLds begins with its ColsLdsT<1>)
+    Lds* L = lds_object<Lds>(lds);
     const float* slabw = L->slabw;
     const unsigned char* slabl = L->slabl;
     const unsigned char* slabp = FUSION ? lds_object<FusLds>(lds)->slabp : L->slabl;
@@ -1102,7 +1157,7 @@ __device__ PHMRF_DP_INLINE unsigned int dp_flagged(StripGeom g, unsigned int lds
       havem |= (inu[p] ? 1u : 0u) << (8 + p);
     }
     DPH(1)
-#define PHMRF_DP_PASS(P_, REC_)                                                                                          \
+#define PHMRF_DP_PASS(P_)                                                                                                \
   if (!(P_ * 64 > t_end || P_ * 64 + 63 < t_lo)) {                                                                     \
     int t = P_ * 64 + lane;                                                                                            \
     asm volatile("" : "+v"(t));                                                                                        \
@@ -1111,16 +1166,20 @@ __device__ PHMRF_DP_INLINE unsigned int dp_flagged(StripGeom g, unsigned int lds
     slab_record<ORIENT, FUSION>(slabw, slabl, slabp, t, ncols, ncell, alpha, (havem >> (8 + P_)) & 1u, ru0[P_], ru1[P_], (havem >> P_) & 1u,   \
                         c0, c1, w4, bits);                                                                             \
     DPH(2)                                                                                                             \
-    dp_pass_chunked<P_, REC_>(m, took, lane, tabch, c0, c1, w4[0], w4[1], w4[2], w4[3], bits, t_lo, t_end, dlo[P_],     \
+    dp_pass_chunked<P_>(m, took, lane, tabch, c0, c1, w4[0], w4[1], w4[2], w4[3], bits, t_lo, t_end, dlo[P_],           \
                               dhi[P_], live, dp_wk, dp_t0);                                                               \
   }
 
+    // ONE walk, which keeps the decision ballots (two v_writelane per step) whether or not a move turns up: a second,
+    // recording walk for the runs that move costs the fusion pass more than that (45 % of its runs move), and the
+    // expansions (9 %) the registers and the code of a second copy of the passes (measured: profiles/strip_dp_walk.json)
     float m = lane == 0 ? 0.f : BIG;
     unsigned long long took = 0ull;
-    unsigned int dlo[NPASS], dhi[NPASS];
+    unsigned int dlo[NPASS], dhi[NPASS];       // (a pass the window does not touch, a chunk that is not live: its lanes stay 0)
 #pragma unroll
     for (int p = 0; p < NPASS; ++p) dlo[p] = dhi[p] = 0u;
-    PHMRF_DP_PASS(0, false) PHMRF_DP_PASS(1, false) PHMRF_DP_PASS(2, false) PHMRF_DP_PASS(3, false) PHMRF_DP_PASS(4, false)
+    PHMRF_DP_PASS(0) PHMRF_DP_PASS(1) PHMRF_DP_PASS(2) PHMRF_DP_PASS(3) PHMRF_DP_PASS(4)
+#undef PHMRF_DP_PASS
     const float mmin = wave_min_f32(m);
     if (!(took & 1ull) && PHMRF_RL(m, 0) == mmin) {
       if (mslot && lane == 0) *mslot = (uint16_t)tick_a;
@@ -1130,16 +1189,12 @@ __device__ PHMRF_DP_INLINE unsigned int dp_flagged(StripGeom g, unsigned int lds
     if (lane == 0) atomicAdd(trace + TRACE_MOVED, 1ull);
 #endif
     DPH(4)
-    // a move exists: walk again, this time recording the decision ballots
+    // a move exists: the end state (lowest profile index among the minima), then the backtrack through the kept ballots
     const int q_end = t_end % 6;
     int sidx = 0;
 #pragma unroll
     for (int j = 0; j < 6; ++j) sidx |= ((state_of_lane(lane) >> ((q_end - j + 6) % 6)) & 1) << j;
-    m = lane == 0 ? 0.f : BIG;
-    PHMRF_DP_PASS(0, true) PHMRF_DP_PASS(1, true) PHMRF_DP_PASS(2, true) PHMRF_DP_PASS(3, true) PHMRF_DP_PASS(4, true)
-#undef PHMRF_DP_PASS
-    const float mmin2 = wave_min_f32(m);
-    const float cand = (m == mmin2) ? (float)sidx : 127.f;
+    const float cand = (m == mmin) ? (float)sidx : 127.f;
     const float best = wave_min_f32(cand);
     int s = state_of_lane(__ffsll((long long)__ballot(cand == best)) - 1);
     unsigned int xsel[NPASS];
