@@ -401,6 +401,40 @@ PHMRF_API int phmrf_diff_domains(const uint8_t* a_dev, const uint8_t* b_dev, con
                                  int64_t* table_host /* [capacity*12] */, int64_t* n_domains,
                                  int64_t* band_counts_host_or_null /* [32*3] */, void* hip_stream);
 
+/* ---- profiling the states ------------------------------------------------------------------------- */
+/* What a state IS, from the block's resident f32 observations x (the uploaded float64 rounded to nearest) and its current
+ * labels (no ABI bump: the calls only add entry points).  Both calls run over the nodes the block OWNS
+ * (all n unless it is a row tile), need observations and labels (PHMRF_ERR_STATE otherwise) and nothing else -- no graph, no
+ * log-likelihoods --, cover every K <= 64 and S <= 16, are queued on the block's stream and return when done.  A node whose
+ * label is >= K (no library call leaves one) is not counted.  The observations are not inspected.
+ *
+ * phmrf_state_hist: one pass of an exact radix selection.  The ORDERABLE KEY of a value with bit pattern b is
+ * b ^ (b >> 31 ? 0xFFFFFFFF : 0x80000000): ascending keys are ascending floats, -0 sorts below +0 (equal as floats) and the
+ * non-finite patterns sort to the two ends by their bits.  shift is 24, 16, 8 or 0 -- the digit (key >> shift) & 255.
+ *   shift == 24: J must be 1 and prefix is ignored; every owned node of state k adds 1 to hist[k][s][0][key_is >> 24] for every s.
+ *   otherwise:   a node adds 1 to hist[k][s][j][(key_is >> shift) & 255] for every slot j with
+ *                (key_is >> (shift + 8)) == prefix[k][s][j]; a slot holding 0xFFFFFFFF matches nothing.
+ * prefix: host u32 [K][S][J]; hist: host u64 [K][S][J][256], overwritten.  Integer arithmetic: the same from run to run.
+ * PHMRF_ERR_INVALID for a shift other than these four, J outside [1, 16], J != 1 at shift 24 or a NULL buffer. */
+PHMRF_API int phmrf_state_hist(phmrf_block_t b, int shift, int J, const uint32_t* prefix /* [K][S][J] */,
+                               uint64_t* hist /* [K][S][J][256] */);
+
+/* phmrf_state_moments: per state k over the owned nodes, in one pass:
+ *   count[k]        host int64 [K]       the nodes with label k
+ *   sum[k][s]       host float64 [K][S]  sum of x_is         sumsq[k][s]  sum of x_is^2 (the square of an f32 is exact in f64)
+ *   bands[k][t]     host int64 [K][PHMRF_DIFF_BANDS] or NULL: the nodes of state k in band t of the distance d = |dist0 + j - i|
+ *                   (band 0: d == 0; band t >= 1: 2^(t-1) <= d < 2^t, as phmrf_diff_domains), (i, j) the node's cell in the
+ *                   block's own geometry.  For a whole block dist0 = start_bin2 - start_bin1.  A row tile of a diagonal block
+ *                   keeps its block's dist0 (rows and columns shift alike); a row tile of a full block whose first STORED row
+ *                   is row r of the unsplit block is given dist0 - r.
+ * The two sums are doubles added in an order that depends on the node count alone (per-wave partials, per-workgroup rows,
+ * the rows added in a fixed order; no floating-point atomics): two calls on the same inputs return the same bytes, with
+ * PHMRF_DETERMINISTIC or without.  Any order of summation is within (count[k] - 1) 2^-53 sum |term| of the exact sum.
+ * PHMRF_ERR_STATE also for bands on a block without grid geometry; PHMRF_ERR_INVALID for a NULL count / sum / sumsq or a
+ * distance of 2^31 or more. */
+PHMRF_API int phmrf_state_moments(phmrf_block_t b, int64_t dist0, int64_t* count /* [K] */, double* sum /* [K][S] */,
+                                  double* sumsq /* [K][S] */, int64_t* bands_or_null /* [K][32] */);
+
 /* ---- pre-processing filters ----------------------------------------------------------------------- */
 /* ABI 127: the raw loader's smoothing filters (phylo_hmrf_amd/preprocess.py) on ONE H x W plane of a
  * contact map, no block: row-major device buffers of H W pixels, pixel units throughout (sigmas, window and radius count

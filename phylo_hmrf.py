@@ -92,6 +92,10 @@ def parse_args(argv=None):
     parser.add_option("--ancestral", default="", help="with --segment: after the segmentation, reconstruct the contact map of "
                       "every internal tree node (posterior: weighted by the state posteriors; called: the called state's own "
                       "map) with its standard deviation, in the model's feature units, and write ancestral_<run_id>_<K>.npz")
+    parser.add_option("--profile", default="0", help="1: after the .mat of a fit or of --segment is written, profile the states "
+                      "of the state_vec it holds on the GPU (counts, exact quantiles, mean and sd per species, distance bands, "
+                      "chromosome enrichment) and write profile_<run_id>_<K>.npz and .txt")
+    parser.add_option("--profile_quantiles", default="0.003,0.25,0.5,0.75,0.997", help="--profile 1: up to 8 quantiles in [0, 1]")
     parser.add_option("--postprocess", default="", help="skip loading data and fitting: smooth the states of this "
                       "estimate_ou_*.mat or segment_*.mat (the reference's processing/*.m), write estimate_test<chrom>.ori.txt, "
                       ".smooth.txt and test<chrom>.region.txt in genome coordinates (--resolution) and smooth_<stem>.mat under --output")
@@ -240,6 +244,35 @@ def check_ancestral(ancestral, segment, postprocess):
                          "its segmentation")
 
 
+def check_profile(profile, profile_quantiles, postprocess, compare):
+    """--profile 1 needs the observations on the GPU: it goes with a fit or --segment -> the quantiles, or None when off"""
+    if str(profile) not in ("0", "1"):
+        raise SystemExit("--profile must be 0 or 1")
+    if str(profile) == "0":
+        return None
+    for name, value in (("--postprocess", postprocess), ("--compare", compare)):
+        if value:
+            raise SystemExit("--profile 1 cannot be combined with %s, which loads no data: the profile needs the observations"
+                             % name)
+    from phylo_hmrf_amd.profile import parse_quantiles
+    try:
+        return parse_quantiles(profile_quantiles)
+    except ValueError as e:
+        raise SystemExit("--profile_quantiles: %s" % e)
+
+
+def write_profile(model, state_vec, quantiles, output_path, run_id, K, species, rank):
+    """profile the written state_vec (a collective: every rank takes part, rank 0 writes)"""
+    from phylo_hmrf_amd import profile as _profile
+    start = time.time()
+    prof = model.state_profile(quantiles=quantiles, state_vec=state_vec)
+    print("profile use time: %s %s" % (time.time() - start, prof["timing"]))
+    if rank == 0:
+        stem = "%s/profile_%d_%d" % (output_path, run_id, K)
+        _profile.save_npz(stem + ".npz", prof, species)
+        _profile.save_txt(stem + ".txt", prof, species)
+
+
 def check_compare(compare, compare_with, compare_field, compare_match, segment, postprocess, ancestral, save_model,
                   filter_device):
     """--compare A.mat --compare_with B.mat reads two finished state maps: it goes with nothing that loads data or fits"""
@@ -264,7 +297,8 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
         init_method="minibatch", warm_start="best", checkpoint="", checkpoint_every="1", resume="", energy_tol_ppb="10000",
         save_model="", segment="", postprocess="", smooth_window="5", smooth_area="-1", smooth_iter="1",
         filter_device="0", ancestral="", compare="", compare_with="", compare_field="state_vec", compare_match="0",
-        compare_min_conf="0", compare_area="-1"):
+        compare_min_conf="0", compare_area="-1", profile="0", profile_quantiles="0.003,0.25,0.5,0.75,0.997"):
+    profile_q = check_profile(profile, profile_quantiles, postprocess, compare)
     check_compare(compare, compare_with, compare_field, compare_match, segment, postprocess, ancestral, save_model,
                   filter_device)
     check_ancestral(ancestral, segment, postprocess)
@@ -394,6 +428,9 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
             if rank == 0:
                 leaves = species if species is not None else seg_model.species
                 save_npz("%s/ancestral_%d_%d.npz" % (output_path, run_id, n_components1), anc, ancestral, len_vec, leaves)
+        if profile_q is not None:
+            write_profile(model, res["state_vec"], profile_q, output_path, run_id, n_components1,
+                          species if species is not None else seg_model.species, rank)
         model.close()
         if world > 1:
             import torch.distributed as dist
@@ -429,6 +466,8 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
             pre = {} if synthetic > 0 else dict(x_max=x_max, resolution=resolution, filter_mode=int(filter_mode),
                                                  filter_sigma=float(filter_sigma), diagonal_type=int(diagonal_type))
             tree1.save_model(save_model, species=species, **pre)
+        if profile_q is not None:
+            write_profile(tree1, state_vec, profile_q, output_path, run_id, n_components1, species, rank)
         print(params_vecList.shape)
         tree1.close()
         mstep.close_pool()
@@ -454,4 +493,5 @@ if __name__ == "__main__":
         postprocess=opts.postprocess, smooth_window=opts.smooth_window, smooth_area=opts.smooth_area,
         smooth_iter=opts.smooth_iter, filter_device=opts.filter_device, ancestral=opts.ancestral,
         compare=opts.compare, compare_with=opts.compare_with, compare_field=opts.compare_field,
-        compare_match=opts.compare_match, compare_min_conf=opts.compare_min_conf, compare_area=opts.compare_area)
+        compare_match=opts.compare_match, compare_min_conf=opts.compare_min_conf, compare_area=opts.compare_area,
+        profile=opts.profile, profile_quantiles=opts.profile_quantiles)

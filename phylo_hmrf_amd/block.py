@@ -323,6 +323,31 @@ class Block(object):
                                       ptr_d(aff), ptr_d(cv), mean.ctypes.data_as(fp), sd.ctypes.data_as(fp) if want_sd else None))
         return mean, sd
 
+    # -- profiling the states (profile.py) ---------------------------------------------------------------
+    def state_hist(self, shift, prefix=None):
+        """one pass of the radix selection over the owned nodes (include/phmrf.h, phmrf_state_hist): prefix uint32 [K, S, J]
+        (None at shift 24: one slot) -> uint64 [K, S, J, 256]"""
+        if prefix is None:
+            prefix = np.zeros((self.K, self.S, 1), dtype=np.uint32)
+        pre = np.ascontiguousarray(prefix, dtype=np.uint32)
+        if pre.ndim != 3 or pre.shape[:2] != (self.K, self.S):
+            raise ValueError("prefix %s is not [K = %d, S = %d, J]" % (pre.shape, self.K, self.S))
+        J = pre.shape[2]
+        hist = np.zeros((self.K, self.S, max(J, 1), 256), dtype=np.uint64)
+        check(self._L.phmrf_state_hist(self._h, int(shift), int(J), pre.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                       hist.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return hist
+
+    def state_moments(self, dist0=0, want_bands=False):
+        """per state over the owned nodes -> (count int64 [K], sum float64 [K, S], sumsq float64 [K, S], bands int64 [K, 32] of
+        the distance |dist0 + j - i| or None); a row tile of a full block passes dist0 minus its first stored row"""
+        count = np.zeros(self.K, dtype=np.int64)
+        total, sq = np.zeros((self.K, self.S)), np.zeros((self.K, self.S))
+        bands = np.zeros((self.K, 32), dtype=np.int64) if want_bands else None
+        check(self._L.phmrf_state_moments(self._h, int(dist0), ptr_i64(count), ptr_d(total), ptr_d(sq),
+                                          ptr_i64(bands) if want_bands else None))
+        return count, total, sq, bands
+
     def posterior_stats_dev(self, beta, estimate_type, out_dev_ptr):
         check(self._L.phmrf_posterior_stats_dev(self._h, float(beta), int(estimate_type), ctypes.c_void_p(out_dev_ptr)))
 

@@ -80,9 +80,6 @@ struct MapB {
   uint8_t to[64];
 };
 
-// band of a distance d >= 0: 0 for d == 0, else t with 2^(t-1) <= d < 2^t
-__device__ __forceinline__ int band_of(long long d) { return d == 0 ? 0 : 64 - __clzll(d); }
-
 // a finite float32 in [0, 1], told by its bits (the library is compiled with -fno-honor-nans: a comparison proves nothing
 // about a NaN): +0 .. 1.0 are the patterns up to 0x3f800000, and -0
 __host__ __device__ __forceinline__ bool unit_bits(uint32_t u) { return u <= 0x3f800000u || u == 0x80000000u; }

@@ -1,4 +1,4 @@
-// What the post-processing's kernel files share (smooth.hip, compare.hip): the capped grid, the wave helpers of their integer
+// What the post-processing's kernel files share (smooth.hip, compare.hip, profile.hip): the capped grid, the wave helpers of their integer
 // accumulations -- one atomic per RUN of equal destination among consecutive lanes, because state maps are piecewise
 // constant -- and the full-matrix area of a grid component.
 #pragma once
@@ -41,6 +41,9 @@ __device__ __forceinline__ void wave_run_add(T* dst, int key, T x) {
   const bool next_head = lane == 63 || ((heads >> (lane + 1)) & 1ull);
   if (key >= 0 && next_head) atomicAdd(dst + key, x - (h > 0 ? before : (T)0));
 }
+
+// band of a distance d >= 0: 0 for d == 0, else t with 2^(t-1) <= d < 2^t (PHMRF_DIFF_BANDS of them below 2^31)
+__device__ __forceinline__ int band_of(long long d) { return d == 0 ? 0 : 64 - __clzll(d); }
 
 // the area on the full matrix of the component with root v, from acc[v] = (weight << 32) | nodes (weight: 1 per diagonal
 // node, 2 per other node) and mirror[v] = a node has j - i <= 1: a diagonal block's component that is its own mirror counts

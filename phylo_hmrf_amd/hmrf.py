@@ -449,6 +449,12 @@ class phyloHMRF(_BaseGraph):
         from .ancestral import reconstruct
         return reconstruct(self, weighting, want_sd)
 
+    def state_profile(self, quantiles=(0.003, 0.25, 0.5, 0.75, 0.997), state_vec=None, want_bands=True):
+        """per state: counts, exact quantiles, mean and sd per species, distance bands, chromosome enrichment, on the labels the
+        device holds or on `state_vec` (profile.py)"""
+        from .profile import state_profile
+        return state_profile(self, quantiles, state_vec, want_bands)
+
     def save_model(self, path, species=None, **preprocessing):
         """the fitted model as a self-contained .npz (model_io.py)"""
         from .model_io import save_model
