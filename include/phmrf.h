@@ -401,6 +401,44 @@ PHMRF_API int phmrf_diff_domains(const uint8_t* a_dev, const uint8_t* b_dev, con
                                  int64_t* table_host /* [capacity*12] */, int64_t* n_domains,
                                  int64_t* band_counts_host_or_null /* [32*3] */, void* hip_stream);
 
+/* ---- the domains of one state map ------------------------------------------------------------------ */
+/* ONE state map of ONE region, no block (no ABI bump: the calls only add entry points).  u8 labels on
+ * the device in the node order of phmrf_smooth_labels.  Both calls are queued on hip_stream (NULL: the null stream), return
+ * when done and use integers only: the results are the same bytes from run to run.
+ *
+ * phmrf_state_adjacency: adj_host[a * K + b] (host int64 [K * K]) = the number of edges of the region's 8-neighbour grid
+ * graph whose two endpoints have the states a and b.  The edges are the block's own STORED ones (both ends stored nodes: in
+ * a diagonal block the edges (i, j) - (i2, j2) with i2 <= j2, each once).  The table is symmetric, its diagonal holds the
+ * edges inside one state, and the sum over a < b is the number of discordant edges the Potts term counts.
+ * PHMRF_ERR_INVALID for a NULL pointer, K < 1, a non-square diagonal block or a label >= K (nothing written);
+ * PHMRF_ERR_UNSUPPORTED for K > 64 or n >= 2^31 - 64. */
+PHMRF_API int phmrf_state_adjacency(const uint8_t* labels_dev, int H, int W, int diagonal, int K,
+                                    int64_t* adj_host /* [K*K] */, void* hip_stream);
+
+/* phmrf_state_domains: the DOMAINS of the map, the 8-connected components of equal state on the region's full (symmetric)
+ * matrix, with the conventions of phmrf_smooth_labels and phmrf_diff_domains: a diagonal block's component with a node at
+ * j - i <= 1 is its own mirror and has area 2 nodes - diagonal nodes; any other component has a twin of equal area and is
+ * listed once.  Domains with area >= min_area are listed in ascending order of their root, the smallest stored node id.
+ *   *n_domains                 the number of listed domains
+ *   n_components_host_or_null  host int64 [K]: ALL components of state k, whatever their area (a twin pair counts once)
+ *   domain_out_dev_or_null     device int32 [n]: the id of the node's listed domain (also when it is >= capacity) or -1
+ *   table_host                 host int64 [capacity * PHMRF_STATE_DOMAIN_COLS]: a row for the first min(*n_domains, capacity):
+ *     0 root   1-4 i0 i1 j0 j1, the inclusive bounding box of the domain's STORED nodes   5 stored nodes   6 area   7 state
+ *     8 boundary edges: the stored 8-neighbour edges from a node of the domain to a node of another state
+ *     9 the state that holds most of those edges (the lowest on ties; -1 when there are none)   10 the edges to that state
+ *     11, 12 the smallest and largest d = |dist0 + j - i| over the stored nodes (dist0 = start_bin2 - start_bin1)
+ *     13 the sum over the nodes of floor(conf 2^24) (exact; 0 without conf_dev_or_null, float32 [n] on the device)   14, 15 0
+ * A component that is not its own mirror has every full-matrix neighbour stored (all of its nodes have j - i >= 2), so
+ * columns 8 - 10 describe its boundary on the full matrix; a self-mirror component's are those of its upper-triangle half.
+ * PHMRF_ERR_INVALID for a label >= K (nothing written), a non-square diagonal block, capacity < 0, min_area < 1, a NULL
+ * table with capacity > 0, a NULL n_domains, a confidence that is not a finite number in [0, 1], or a distance of 2^31 or
+ * more; PHMRF_ERR_UNSUPPORTED for K > 64 or n >= 2^31 - 64. */
+#define PHMRF_STATE_DOMAIN_COLS 16
+PHMRF_API int phmrf_state_domains(const uint8_t* labels_dev, const float* conf_dev_or_null, int H, int W, int diagonal,
+                                  int64_t dist0, int K, int64_t min_area, int32_t* domain_out_dev_or_null /* [n] */,
+                                  int64_t capacity, int64_t* table_host /* [capacity*16] */, int64_t* n_domains,
+                                  int64_t* n_components_host_or_null /* [K] */, void* hip_stream);
+
 /* ---- profiling the states ------------------------------------------------------------------------- */
 /* What a state IS, from the block's resident f32 observations x (the uploaded float64 rounded to nearest) and its current
  * labels (no ABI bump: the calls only add entry points).  Both calls run over the nodes the block OWNS

@@ -117,6 +117,12 @@ def parse_args(argv=None):
                       "reach this (0: every differing bin pair counts)")
     parser.add_option("--compare_area", default="-1", help="--compare: smallest area of a listed domain (-1: one more than the "
                       "smoothing's small-region area, 81, or 26 for a region less than 100 bins high)")
+    parser.add_option("--domains", default="", help="skip loading data and fitting: list the domains of the states of this "
+                      ".mat (the 8-connected same-state regions of every region's full matrix: box, area, boundary, distance "
+                      "range) and count the edges between every pair of states; writes domains_<stem>.mat and "
+                      "domains_<stem>.txt in genome coordinates (--resolution) under --output")
+    parser.add_option("--domains_field", default="state_vec", help="--domains: state_vec or state_vec_smooth")
+    parser.add_option("--domains_area", default="-1", help="--domains: smallest area of a listed domain (-1: as --compare_area)")
     parser.add_option("-h", "--help", action="help")
     opts, _ = parser.parse_args(argv)
     return opts
@@ -290,6 +296,19 @@ def check_compare(compare, compare_with, compare_field, compare_match, segment, 
         raise SystemExit("--compare_match must be 0 or 1")
 
 
+def check_domains(domains, domains_field, segment, postprocess, compare, ancestral, save_model, profile, filter_device):
+    """--domains FILE.mat reads one finished state map: it goes with nothing that loads data or fits"""
+    if not domains:
+        return
+    for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare),
+                        ("--ancestral", ancestral), ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
+                        ("--filter_device 1", str(filter_device) == "1")):
+        if value:
+            raise SystemExit("--domains cannot be combined with %s: it loads no data and fits nothing" % name)
+    if domains_field not in ("state_vec", "state_vec_smooth"):
+        raise SystemExit("--domains_field must be state_vec or state_vec_smooth, not %r" % (domains_field,))
+
+
 def run(num_states, chromvec, root_path, multiple, species_name, sort_states, run_id1, cons_param, method_mode,
         initial_mode, initial_weight, initial_weight1, initial_magnitude, position1, position2, filter_sigma, beta,
         beta1, num_neighbor, filter_mode, conv_threshold, estimate_type, simu_version, annotation, reload_mode,
@@ -297,7 +316,10 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
         init_method="minibatch", warm_start="best", checkpoint="", checkpoint_every="1", resume="", energy_tol_ppb="10000",
         save_model="", segment="", postprocess="", smooth_window="5", smooth_area="-1", smooth_iter="1",
         filter_device="0", ancestral="", compare="", compare_with="", compare_field="state_vec", compare_match="0",
-        compare_min_conf="0", compare_area="-1", profile="0", profile_quantiles="0.003,0.25,0.5,0.75,0.997"):
+        compare_min_conf="0", compare_area="-1", profile="0", profile_quantiles="0.003,0.25,0.5,0.75,0.997",
+        domains="", domains_field="state_vec", domains_area="-1"):
+    check_domains(domains, domains_field, segment, postprocess, compare or compare_with, ancestral, save_model, profile,
+                  filter_device)
     profile_q = check_profile(profile, profile_quantiles, postprocess, compare)
     check_compare(compare, compare_with, compare_field, compare_match, segment, postprocess, ancestral, save_model,
                   filter_device)
@@ -308,6 +330,13 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
     if filter_device and (int(reload_mode) == 1 or int(synthetic) > 0 or postprocess):
         raise SystemExit("--filter_device 1 runs the raw loader's filter on the GPU: it cannot be combined with --reload 1, "
                          "--synthetic or --postprocess, where nothing is filtered")
+    if domains:
+        from phylo_hmrf_amd.domains import domains_files
+        area = int(domains_area)
+        out = domains_files(domains, str(output_path), int(resolution), field=domains_field,
+                            min_area=None if area == -1 else area)
+        print("domains written: %s" % out)
+        return out
     if compare:
         from phylo_hmrf_amd.compare import compare_files
         area = int(compare_area)
@@ -494,4 +523,5 @@ if __name__ == "__main__":
         smooth_iter=opts.smooth_iter, filter_device=opts.filter_device, ancestral=opts.ancestral,
         compare=opts.compare, compare_with=opts.compare_with, compare_field=opts.compare_field,
         compare_match=opts.compare_match, compare_min_conf=opts.compare_min_conf, compare_area=opts.compare_area,
-        profile=opts.profile, profile_quantiles=opts.profile_quantiles)
+        profile=opts.profile, profile_quantiles=opts.profile_quantiles, domains=opts.domains,
+        domains_field=opts.domains_field, domains_area=opts.domains_area)

@@ -80,11 +80,6 @@ struct MapB {
   uint8_t to[64];
 };
 
-// a finite float32 in [0, 1], told by its bits (the library is compiled with -fno-honor-nans: a comparison proves nothing
-// about a NaN): +0 .. 1.0 are the patterns up to 0x3f800000, and -0
-__host__ __device__ __forceinline__ bool unit_bits(uint32_t u) { return u <= 0x3f800000u || u == 0x80000000u; }
-__device__ __forceinline__ bool unit_conf(float c) { return unit_bits(__float_as_uint(c)); }
-
 // diff[v] and the band counts; bad |= 1 for a label >= K, 2 for a confidence that is not a finite number in [0, 1]
 __global__ __launch_bounds__(256) void compare_diff_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, MapB map,
                                                            const float* __restrict__ conf_a, const float* __restrict__ conf_b,

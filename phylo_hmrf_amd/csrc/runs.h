@@ -1,4 +1,4 @@
-// What the post-processing's kernel files share (smooth.hip, compare.hip, profile.hip): the capped grid, the wave helpers of their integer
+// What the post-processing's kernel files share (smooth.hip, compare.hip, profile.hip, domains.hip): the capped grid, the wave helpers of their integer
 // accumulations -- one atomic per RUN of equal destination among consecutive lanes, because state maps are piecewise
 // constant -- and the full-matrix area of a grid component.
 #pragma once
@@ -53,6 +53,11 @@ __device__ __forceinline__ long long component_area(int64_t v, int diagonal, con
   const unsigned long long a = acc[v];
   return (diagonal && mirror[v]) ? (long long)(a >> 32) : (long long)(a & 0xffffffffull);
 }
+
+// a finite float32 in [0, 1], told by its bits (the library is compiled with -fno-honor-nans: a comparison proves nothing
+// about a NaN): +0 .. 1.0 are the patterns up to 0x3f800000, and -0
+__host__ __device__ __forceinline__ bool unit_bits(uint32_t u) { return u <= 0x3f800000u || u == 0x80000000u; }
+__device__ __forceinline__ bool unit_conf(float c) { return unit_bits(__float_as_uint(c)); }
 
 template <typename T>
 int alloc(T** p, size_t count) {
