@@ -439,6 +439,30 @@ PHMRF_API int phmrf_state_domains(const uint8_t* labels_dev, const float* conf_d
                                   int64_t capacity, int64_t* table_host /* [capacity*16] */, int64_t* n_domains,
                                   int64_t* n_components_host_or_null /* [K] */, void* hip_stream);
 
+/* phmrf_render_states: the state map of ONE region as an image, reduced by the integer `factor` f >= 1 (DESIGN.md section 7;
+ * no block, no ABI bump).  The full matrix M is the H x W block itself, or for a diagonal block the symmetric matrix
+ * M[i][j] = the stored node (min(i, j), max(i, j)); conf_dev_or_null (float32 [n]) and mark_dev_or_null (u8 [n]) are
+ * mirrored alike.  The image has h = ceil(H / f) rows and w = ceil(W / f) columns, pixel (p, q) covers the cells
+ * [p f, min(H, (p + 1) f)) x [q f, min(W, (q + 1) f)); row 0 is the top row.
+ *   planes_host_or_null  host u8 [3][h w]:
+ *     state   the state most of the pixel's cells hold, the lowest on ties
+ *     conf8   floor(255 S / (c 2^24)) with c the number of the pixel's cells in that state and S the sum of floor(conf 2^24)
+ *             over them (exact, u64); 255 without conf
+ *     mark8   1 when a cell of the pixel has mark != 0, else 0
+ *   rgb_host_or_null     host u8 [h w 3]: the highlight colour (extra_host[0..2]) for a marked pixel; else, with outline != 0,
+ *     the outline colour (extra_host[3..5]) for a pixel whose state differs from its right or its lower neighbour's; else per
+ *     channel 255 - ((255 - palette_host[3 state + c]) t) / 255 with t = 64 + (191 conf8) / 255, integer divisions: the
+ *     palette colour itself at full confidence, faded towards white below
+ * Both outputs NULL: the call only checks its input.  Integers only: the same bytes from run to run.
+ * PHMRF_ERR_INVALID for a NULL label, palette or extra-colour pointer, H < 1, W < 1, a non-square diagonal block, K outside
+ * [1, 64], factor < 1, a label >= K or a confidence that is not a finite number in [0, 1] (nothing written);
+ * PHMRF_ERR_UNSUPPORTED for factor > 32768 (a pixel's count stays below 2^31) or h w >= 2^31 - 64. */
+PHMRF_API int phmrf_render_states(const uint8_t* labels_dev, const float* conf_dev_or_null, const uint8_t* mark_dev_or_null,
+                                  int H, int W, int diagonal, int K, int factor, const uint8_t* palette_host /* [K*3] */,
+                                  const uint8_t* extra_host /* [6]: highlight, outline */, int outline,
+                                  uint8_t* planes_host_or_null /* [3][h*w]: state, conf8, mark8 */,
+                                  uint8_t* rgb_host_or_null /* [h*w*3] */, void* hip_stream);
+
 /* ---- profiling the states ------------------------------------------------------------------------- */
 /* What a state IS, from the block's resident f32 observations x (the uploaded float64 rounded to nearest) and its current
  * labels (no ABI bump: the calls only add entry points).  Both calls run over the nodes the block OWNS

@@ -123,6 +123,18 @@ def parse_args(argv=None):
                       "domains_<stem>.txt in genome coordinates (--resolution) under --output")
     parser.add_option("--domains_field", default="state_vec", help="--domains: state_vec or state_vec_smooth")
     parser.add_option("--domains_area", default="-1", help="--domains: smallest area of a listed domain (-1: as --compare_area)")
+    parser.add_option("--render", default="", help="skip loading data and fitting: draw the states of this .mat, one PNG per "
+                      "region of the region's full matrix reduced to at most --render_side pixels a side (a pixel takes the "
+                      "state most of its bin pairs hold); writes render_<stem>_r<region>_chr<chrom>.png, render_<stem>.npz "
+                      "and render_<stem>_legend.txt under --output")
+    parser.add_option("--render_field", default="state_vec", help="--render: state_vec or state_vec_smooth")
+    parser.add_option("--render_side", default="2048", help="--render: the largest side of an image in pixels (>= 1)")
+    parser.add_option("--render_colors", default="", help="--render: a text file of R G B rows (0 .. 255), one per state, in "
+                      "place of the built-in palette")
+    parser.add_option("--render_outline", default="0", help="--render: 1 = draw the borders between states in black")
+    parser.add_option("--render_conf", default="0", help="--render: 1 = fade every pixel towards white by the file's conf")
+    parser.add_option("--render_mark", default="", help="--render: a compare_*.mat on the same regions; the bin pairs of its "
+                      "differential domains (diff_vec == 2) are highlighted")
     parser.add_option("-h", "--help", action="help")
     opts, _ = parser.parse_args(argv)
     return opts
@@ -309,6 +321,30 @@ def check_domains(domains, domains_field, segment, postprocess, compare, ancestr
         raise SystemExit("--domains_field must be state_vec or state_vec_smooth, not %r" % (domains_field,))
 
 
+def check_render(render, render_field, render_side, render_outline, render_conf, segment, postprocess, compare, domains,
+                 ancestral, save_model, profile, filter_device):
+    """--render FILE.mat reads one finished state map: it goes with nothing that loads data or fits -> the side, or None"""
+    if not render:
+        return None
+    for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
+                        ("--ancestral", ancestral), ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
+                        ("--filter_device 1", str(filter_device) == "1")):
+        if value:
+            raise SystemExit("--render cannot be combined with %s: it loads no data and fits nothing" % name)
+    if render_field not in ("state_vec", "state_vec_smooth"):
+        raise SystemExit("--render_field must be state_vec or state_vec_smooth, not %r" % (render_field,))
+    for name, value in (("--render_outline", render_outline), ("--render_conf", render_conf)):
+        if str(value) not in ("0", "1"):
+            raise SystemExit("%s must be 0 or 1" % name)
+    try:
+        side = int(render_side)
+    except ValueError:
+        side = 0
+    if side < 1:
+        raise SystemExit("--render_side must be an integer >= 1, not %r" % (render_side,))
+    return side
+
+
 def run(num_states, chromvec, root_path, multiple, species_name, sort_states, run_id1, cons_param, method_mode,
         initial_mode, initial_weight, initial_weight1, initial_magnitude, position1, position2, filter_sigma, beta,
         beta1, num_neighbor, filter_mode, conv_threshold, estimate_type, simu_version, annotation, reload_mode,
@@ -317,7 +353,10 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
         save_model="", segment="", postprocess="", smooth_window="5", smooth_area="-1", smooth_iter="1",
         filter_device="0", ancestral="", compare="", compare_with="", compare_field="state_vec", compare_match="0",
         compare_min_conf="0", compare_area="-1", profile="0", profile_quantiles="0.003,0.25,0.5,0.75,0.997",
-        domains="", domains_field="state_vec", domains_area="-1"):
+        domains="", domains_field="state_vec", domains_area="-1", render="", render_field="state_vec", render_side="2048",
+        render_colors="", render_outline="0", render_conf="0", render_mark=""):
+    side = check_render(render, render_field, render_side, render_outline, render_conf, segment, postprocess,
+                        compare or compare_with, domains, ancestral, save_model, profile, filter_device)
     check_domains(domains, domains_field, segment, postprocess, compare or compare_with, ancestral, save_model, profile,
                   filter_device)
     profile_q = check_profile(profile, profile_quantiles, postprocess, compare)
@@ -330,6 +369,12 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
     if filter_device and (int(reload_mode) == 1 or int(synthetic) > 0 or postprocess):
         raise SystemExit("--filter_device 1 runs the raw loader's filter on the GPU: it cannot be combined with --reload 1, "
                          "--synthetic or --postprocess, where nothing is filtered")
+    if render:
+        from phylo_hmrf_amd.render import render_files
+        out = render_files(render, str(output_path), field=render_field, max_side=side, palette_path=render_colors,
+                           outline=str(render_outline) == "1", use_conf=str(render_conf) == "1", mark_path=render_mark)
+        print("images written: %s" % out)
+        return out
     if domains:
         from phylo_hmrf_amd.domains import domains_files
         area = int(domains_area)
@@ -524,4 +569,6 @@ if __name__ == "__main__":
         compare=opts.compare, compare_with=opts.compare_with, compare_field=opts.compare_field,
         compare_match=opts.compare_match, compare_min_conf=opts.compare_min_conf, compare_area=opts.compare_area,
         profile=opts.profile, profile_quantiles=opts.profile_quantiles, domains=opts.domains,
-        domains_field=opts.domains_field, domains_area=opts.domains_area)
+        domains_field=opts.domains_field, domains_area=opts.domains_area, render=opts.render,
+        render_field=opts.render_field, render_side=opts.render_side, render_colors=opts.render_colors,
+        render_outline=opts.render_outline, render_conf=opts.render_conf, render_mark=opts.render_mark)
