@@ -463,6 +463,27 @@ PHMRF_API int phmrf_render_states(const uint8_t* labels_dev, const float* conf_d
                                   uint8_t* planes_host_or_null /* [3][h*w]: state, conf8, mark8 */,
                                   uint8_t* rgb_host_or_null /* [h*w*3] */, void* hip_stream);
 
+/* phmrf_state_tracks: the state map of ONE region projected onto its two genome axes (no block, no ABI
+ * bump).  The full matrix M is the H x W block itself, or for a diagonal block the symmetric matrix M[i][j] = the stored node
+ * (min(i, j), max(i, j)), as in phmrf_render_states.  Cell (i, j) has the distance d = |dist0 + j - i| in bins (dist0 =
+ * start_bin2 - start_bin1) and is INSIDE the window when d_min <= d and (d_max == -1 or d <= d_max).
+ *   rows_host           host int64 [H K]: rows[i][k] = the j in [0, W) with (i, j) inside the window and M[i][j] == k
+ *   cols_host_or_null   host int64 [W K]: cols[j][k] = the i in [0, H) with (i, j) inside the window and M[i][j] == k.  A
+ *                       diagonal block has cols == rows: the pointer is ignored and only rows_host is written.  There a
+ *                       stored node (i, j) with i < j adds 1 to rows[i][k] and to rows[j][k], a node of the diagonal 1 to
+ *                       rows[i][k].
+ * With the window (0, -1) an off-diagonal block has sum(rows) == sum(cols) == n and a diagonal block sum(rows) == H H.
+ * Nodes outside the window are never inspected: a label >= K there is no error and changes no count, and a tile of the
+ * kernel that lies wholly outside the window is not read at all.  Queued on hip_stream, returns when done.  Integers only:
+ * the same bytes from run to run.
+ * PHMRF_ERR_INVALID (nothing written) for a NULL labels_dev or rows_host, a NULL cols_host_or_null on an off-diagonal block,
+ * H < 1, W < 1, K < 1, a non-square diagonal block, a diagonal block with dist0 != 0, d_min < 0, d_max < d_min unless d_max is
+ * -1, or a node inside the window whose label is >= K; PHMRF_ERR_UNSUPPORTED for K > 64, n >= 2^31 - 64 or
+ * |dist0| + H + W >= 2^31. */
+PHMRF_API int phmrf_state_tracks(const uint8_t* labels_dev, int H, int W, int diagonal, int64_t dist0, int K, int64_t d_min,
+                                 int64_t d_max /* -1: no upper limit */, int64_t* rows_host /* [H*K] */,
+                                 int64_t* cols_host_or_null /* [W*K]; ignored for a diagonal block */, void* hip_stream);
+
 /* ---- profiling the states ------------------------------------------------------------------------- */
 /* What a state IS, from the block's resident f32 observations x (the uploaded float64 rounded to nearest) and its current
  * labels (no ABI bump: the calls only add entry points).  Both calls run over the nodes the block OWNS

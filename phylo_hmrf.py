@@ -135,6 +135,13 @@ def parse_args(argv=None):
     parser.add_option("--render_conf", default="0", help="--render: 1 = fade every pixel towards white by the file's conf")
     parser.add_option("--render_mark", default="", help="--render: a compare_*.mat on the same regions; the bin pairs of its "
                       "differential domains (diff_vec == 2) are highlighted")
+    parser.add_option("--tracks", default="", help="skip loading data and fitting: project the states of this .mat onto the "
+                      "genome, per bin the state composition of the bin's row of the contact matrix within each window of "
+                      "--tracks_dist; writes tracks_<stem>.npz and one tracks_<stem>_w<window>.txt per window in genome "
+                      "coordinates (--resolution) under --output")
+    parser.add_option("--tracks_field", default="state_vec", help="--tracks: state_vec or state_vec_smooth")
+    parser.add_option("--tracks_dist", default="0-", help="--tracks: at most 8 windows of genomic distance in bp, lo-hi or lo- "
+                      "(no upper limit), separated by commas; the default 0- is every distance")
     parser.add_option("-h", "--help", action="help")
     opts, _ = parser.parse_args(argv)
     return opts
@@ -345,6 +352,26 @@ def check_render(render, render_field, render_side, render_outline, render_conf,
     return side
 
 
+def check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment, postprocess, compare, domains, ancestral,
+                 save_model, profile, filter_device):
+    """--tracks FILE.mat reads one finished state map: it goes with nothing that loads data or fits -> the windows in bins,
+    or None"""
+    if not tracks:
+        return None
+    for name, value in (("--render", render), ("--segment", segment), ("--postprocess", postprocess), ("--compare", compare),
+                        ("--domains", domains), ("--ancestral", ancestral), ("--save_model", save_model),
+                        ("--profile 1", str(profile) == "1"), ("--filter_device 1", str(filter_device) == "1")):
+        if value:
+            raise SystemExit("--tracks cannot be combined with %s: it loads no data and fits nothing" % name)
+    if tracks_field not in ("state_vec", "state_vec_smooth"):
+        raise SystemExit("--tracks_field must be state_vec or state_vec_smooth, not %r" % (tracks_field,))
+    from phylo_hmrf_amd.tracks import parse_windows
+    try:
+        return parse_windows(tracks_dist, int(resolution))
+    except ValueError as e:
+        raise SystemExit("--tracks_dist: %s" % e)
+
+
 def run(num_states, chromvec, root_path, multiple, species_name, sort_states, run_id1, cons_param, method_mode,
         initial_mode, initial_weight, initial_weight1, initial_magnitude, position1, position2, filter_sigma, beta,
         beta1, num_neighbor, filter_mode, conv_threshold, estimate_type, simu_version, annotation, reload_mode,
@@ -354,7 +381,10 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
         filter_device="0", ancestral="", compare="", compare_with="", compare_field="state_vec", compare_match="0",
         compare_min_conf="0", compare_area="-1", profile="0", profile_quantiles="0.003,0.25,0.5,0.75,0.997",
         domains="", domains_field="state_vec", domains_area="-1", render="", render_field="state_vec", render_side="2048",
-        render_colors="", render_outline="0", render_conf="0", render_mark=""):
+        render_colors="", render_outline="0", render_conf="0", render_mark="", tracks="", tracks_field="state_vec",
+        tracks_dist="0-"):
+    check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment, postprocess, compare or compare_with, domains,
+                 ancestral, save_model, profile, filter_device)
     side = check_render(render, render_field, render_side, render_outline, render_conf, segment, postprocess,
                         compare or compare_with, domains, ancestral, save_model, profile, filter_device)
     check_domains(domains, domains_field, segment, postprocess, compare or compare_with, ancestral, save_model, profile,
@@ -369,6 +399,11 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
     if filter_device and (int(reload_mode) == 1 or int(synthetic) > 0 or postprocess):
         raise SystemExit("--filter_device 1 runs the raw loader's filter on the GPU: it cannot be combined with --reload 1, "
                          "--synthetic or --postprocess, where nothing is filtered")
+    if tracks:
+        from phylo_hmrf_amd.tracks import tracks_files
+        out = tracks_files(tracks, str(output_path), int(resolution), field=tracks_field, windows_bp=tracks_dist)
+        print("tracks written: %s" % out)
+        return out
     if render:
         from phylo_hmrf_amd.render import render_files
         out = render_files(render, str(output_path), field=render_field, max_side=side, palette_path=render_colors,
@@ -571,4 +606,5 @@ if __name__ == "__main__":
         profile=opts.profile, profile_quantiles=opts.profile_quantiles, domains=opts.domains,
         domains_field=opts.domains_field, domains_area=opts.domains_area, render=opts.render,
         render_field=opts.render_field, render_side=opts.render_side, render_colors=opts.render_colors,
-        render_outline=opts.render_outline, render_conf=opts.render_conf, render_mark=opts.render_mark)
+        render_outline=opts.render_outline, render_conf=opts.render_conf, render_mark=opts.render_mark,
+        tracks=opts.tracks, tracks_field=opts.tracks_field, tracks_dist=opts.tracks_dist)

@@ -1,0 +1,261 @@
+// gfx950 kernel that projects ONE state map of one region onto its two genome axes (phmrf_state_tracks).
+// Integer arithmetic throughout: no result depends on the order in which the atomics land.
+//
+//   count    rows[i][k] / cols[j][k]: the cells of row i / column j of the region's full matrix M (a diagonal block:
+//            M[i][j] = the stored node (min(i, j), max(i, j))) that hold state k and lie INSIDE the distance window
+//            d_lo <= |dist0 + j - i| <= d_hi.  A workgroup owns a TILE of TRACKS_TILE_H storage rows by TRACKS_TILE_W storage
+//            columns, the tiles stride over a capped grid.  A tile wholly outside the window is left without a load, a tile
+//            wholly inside it drops the per-cell test.  A wave takes every fourth storage row of the tile, one at a time, and
+//            issues the loads of all its rows before it counts the first.  Per row: up to three head bytes to the next
+//            4-byte boundary of the row's address, then one 4-byte load per lane (four labels), then up to three tail bytes;
+//            the head and tail go byte-wise on the first lanes.  So the lanes of a wave hold distinct columns of ONE row.
+//            Two u32 tables in LDS, (tile row, state) and (tile column, state), both with a row stride of TRACKS_STRIDE = 65
+//            words.  The row table takes ONE atomic per run of equal state among consecutive lanes (wave_run_add; what is
+//            left of a lane's four after a change of state goes in singly).  The column table takes one atomic per cell;
+//            only other waves can hit the same word.  The lanes take their four columns in a rotated order (lane >> 3), so
+//            that 32 lanes of equal state fall on 32 banks instead of 8.
+//            The flush adds every non-zero word of the two tables to the device table with one global atomic and zeroes it.
+//            A diagonal block has one device table: a stored node (i, j) with i < j counts for bin i (row table) and for bin
+//            j (column table, flushed into the same rows), a node of the diagonal for bin i alone.  Its tiles are the upper
+//            triangle of the grid of TRACKS_TILE_W-square super-tiles, TRACKS_TILE_W / TRACKS_TILE_H tiles each.
+//            A label >= K inside the window sets a flag; nodes outside the window are not inspected.
+
+#include "runs.h"
+
+#include <climits>
+
+namespace phmrf {
+namespace {
+
+constexpr int TRACKS_GRID_CAP = 1024;    // workgroups of the kernel (tracks.py GRID_CAP)
+constexpr int TRACKS_TILE_H = 32;        // storage rows of a tile (tracks.py TILE_H)
+constexpr int TRACKS_TILE_W = 256;       // storage columns of a tile: 64 lanes x 4 labels (tracks.py TILE_W)
+constexpr int TRACKS_STRIDE = 65;        // u32 words per tile row / column: 64 states and one word that keeps neighbours off one bank
+constexpr int TRACKS_ROWS_PER_WAVE = TRACKS_TILE_H / 4;          // a workgroup is four waves
+constexpr int TRACKS_PER_SUPER = TRACKS_TILE_W / TRACKS_TILE_H;   // tiles of a square super-tile (diagonal blocks)
+
+// rows [i0, i1) and columns [j0, j1) of the storage; whole: every cell is inside the window
+struct TracksTile {
+  int i0, i1, j0, j1;
+  bool whole;
+};
+
+// the stored cells of row i of a tile: columns [ja, ja + nc) at p; `head` bytes (at most three) up to the next 4-byte boundary
+// of the address, nvec aligned words, then the bytes from `tail` on: nbytes = head + what follows the words
+struct TracksRow {
+  const uint8_t* p;
+  int ja, head, nvec, tail, nbytes;
+};
+
+__device__ __forceinline__ TracksRow tracks_row(const uint8_t* __restrict__ labels, const TracksTile& t, int i, int W, int diagonal) {
+  TracksRow r;
+  r.ja = (diagonal && t.j0 < i) ? i : t.j0;
+  const int nc = t.j1 - r.ja;                          // >= 1: a diagonal block's tile ends right of the diagonal
+  r.p = labels + grid_id<int64_t>(i, r.ja, W, diagonal);
+  r.head = (int)((4 - (reinterpret_cast<uintptr_t>(r.p) & 3)) & 3);
+  if (r.head > nc) r.head = nc;
+  r.nvec = (nc - r.head) >> 2;
+  r.tail = r.head + 4 * r.nvec;
+  r.nbytes = r.head + (nc - r.tail);
+  return r;
+}
+
+// tile T of the region; false for a tile of the last super-tile row's padding, and for a tile wholly outside the window
+// (the same answer for the whole workgroup)
+__device__ __forceinline__ bool tracks_tile(int64_t T, int H, int W, int diagonal, int per_row, int dist0, int d_lo, int d_hi,
+                                            TracksTile* t) {
+  int ti, tj;
+  if (diagonal) {                                      // the upper triangle of the per_row x per_row grid of super-tiles
+    int g;
+    grid_coords(T / TRACKS_PER_SUPER, per_row, 1, &g, &tj);
+    ti = g * TRACKS_PER_SUPER + (int)(T % TRACKS_PER_SUPER);
+  } else {
+    grid_coords(T, per_row, 0, &ti, &tj);
+  }
+  const int64_t i0 = (int64_t)ti * TRACKS_TILE_H;
+  if (i0 >= H) return false;
+  int64_t j0 = (int64_t)tj * TRACKS_TILE_W;
+  const int64_t i1 = i0 + TRACKS_TILE_H < H ? i0 + TRACKS_TILE_H : H;
+  const int64_t j1 = j0 + TRACKS_TILE_W < W ? j0 + TRACKS_TILE_W : W;
+  t->i0 = (int)i0;
+  t->i1 = (int)i1;
+  t->j0 = (int)j0;
+  t->j1 = (int)j1;
+  if (diagonal && j0 < i0) j0 = i0;                    // the stored cells of the tile start at the diagonal
+  if (j0 >= j1) return false;
+  // the range of dist0 + j - i over the tile (|dist0| + H + W < 2^31: an int holds every distance)
+  const int x_lo = dist0 + (int)j0 - ((int)i1 - 1), x_hi = dist0 + ((int)j1 - 1) - (int)i0;
+  const int a_lo = x_lo < 0 ? -x_lo : x_lo, a_hi = x_hi < 0 ? -x_hi : x_hi;
+  const int far = a_lo > a_hi ? a_lo : a_hi;
+  const int near = (x_lo <= 0 && x_hi >= 0) ? 0 : (a_lo < a_hi ? a_lo : a_hi);
+  if (far < d_lo || near > d_hi) return false;
+  t->whole = near >= d_lo && far <= d_hi;
+  return true;
+}
+
+// table: u32 [(H + W) K], the rows' counts and then the columns' (a diagonal block: [H K]); d_hi: INT_MAX for no upper limit
+__global__ __launch_bounds__(256) void tracks_kernel(const uint8_t* __restrict__ labels, int H, int W, int diagonal, int dist0,
+                                                     int K, int d_lo, int d_hi, int per_row, int64_t ntiles,
+                                                     unsigned* __restrict__ table, int* __restrict__ bad) {
+  __shared__ unsigned row_tab[TRACKS_TILE_H * TRACKS_STRIDE];
+  __shared__ unsigned col_tab[TRACKS_TILE_W * TRACKS_STRIDE];
+  for (int t = threadIdx.x; t < TRACKS_TILE_H * TRACKS_STRIDE; t += 256) row_tab[t] = 0;
+  for (int t = threadIdx.x; t < TRACKS_TILE_W * TRACKS_STRIDE; t += 256) col_tab[t] = 0;
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int rot = (lane >> 3) & 3;
+  unsigned* const col_out = table + (diagonal ? (size_t)0 : (size_t)H * K);
+  bool wrong = false;
+  for (int64_t T = blockIdx.x; T < ntiles; T += gridDim.x) {
+    TracksTile t;
+    if (!tracks_tile(T, H, W, diagonal, per_row, dist0, d_lo, d_hi, &t)) continue;
+    // the wave's rows i0 + wave, i0 + wave + 4, ...: every load of the tile is issued before the first count
+    uint32_t word[TRACKS_ROWS_PER_WAVE];
+    int single[TRACKS_ROWS_PER_WAVE];
+#pragma unroll
+    for (int u = 0; u < TRACKS_ROWS_PER_WAVE; ++u) {
+      const int i = t.i0 + wave + 4 * u;
+      word[u] = 0;
+      single[u] = 0;
+      if (i < t.i1) {                                                  // (everything but `lane` is the same for the wave)
+        const TracksRow r = tracks_row(labels, t, i, W, diagonal);
+        if (lane < r.nvec) word[u] = *reinterpret_cast<const uint32_t*>(r.p + r.head + 4 * lane);
+        if (lane < r.nbytes) single[u] = r.p[lane < r.head ? lane : r.tail + (lane - r.head)];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < TRACKS_ROWS_PER_WAVE; ++u) {
+      const int i = t.i0 + wave + 4 * u;
+      if (i >= t.i1) break;
+      const TracksRow r = tracks_row(labels, t, i, W, diagonal);
+      const int row_key = (i - t.i0) * TRACKS_STRIDE;
+      const int x0 = dist0 - i;                                         // the cell's distance is |x0 + j|
+      // one cell: -1 outside the window or with a label >= K, else the state; the column table takes it here
+      auto cell = [&](int s, int j) -> int {
+        if (!t.whole) {
+          const int x = x0 + j, d = x < 0 ? -x : x;
+          if (d < d_lo || d > d_hi) return -1;
+        }
+        if (s >= K) {
+          wrong = true;
+          return -1;
+        }
+        if (!diagonal || j != i) atomicAdd(col_tab + (j - t.j0) * TRACKS_STRIDE + s, 1u);
+        return s;
+      };
+      if (r.nvec > 0) {
+        int key[4] = {-1, -1, -1, -1};
+        if (lane < r.nvec) {
+          const uint32_t w = __builtin_rotateright32(word[u], 8 * rot);
+          const int j = r.ja + r.head + 4 * lane;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int s = cell((int)((w >> (8 * e)) & 0xff), j + ((e + rot) & 3));
+            key[e] = s < 0 ? -1 : row_key + s;
+          }
+        }
+        unsigned lead = key[0] >= 0 ? 1u : 0u;          // the lane's cells in the state of its first
+        int e = 1;
+        for (; e < 4 && lead && key[e] == key[0]; ++e) ++lead;
+        wave_run_add(row_tab, key[0], lead);
+        for (; e < 4; ++e)
+          if (key[e] >= 0) atomicAdd(row_tab + key[e], 1u);
+      }
+      if (r.nbytes > 0) {
+        int key = -1;
+        if (lane < r.nbytes) {
+          const int s = cell(single[u], r.ja + (lane < r.head ? lane : r.tail + (lane - r.head)));
+          key = s < 0 ? -1 : row_key + s;
+        }
+        wave_run_add(row_tab, key, key >= 0 ? 1u : 0u);
+      }
+    }
+    __syncthreads();
+    const int nr = t.i1 - t.i0, ncol = t.j1 - t.j0;
+    for (int x = threadIdx.x; x < nr * K; x += 256) {
+      const int r = x / K, s = x - r * K;
+      const unsigned c = row_tab[r * TRACKS_STRIDE + s];
+      if (c) {
+        atomicAdd(table + (size_t)(t.i0 + r) * K + s, c);
+        row_tab[r * TRACKS_STRIDE + s] = 0;
+      }
+    }
+    for (int x = threadIdx.x; x < ncol * K; x += 256) {
+      const int r = x / K, s = x - r * K;
+      const unsigned c = col_tab[r * TRACKS_STRIDE + s];
+      if (c) {
+        atomicAdd(col_out + (size_t)(t.j0 + r) * K + s, c);
+        col_tab[r * TRACKS_STRIDE + s] = 0;
+      }
+    }
+    __syncthreads();
+  }
+  if (wrong) atomicOr(bad, 1);
+}
+
+// device buffers of one call, released on every way out
+struct TracksWork {
+  unsigned* table = nullptr;
+  int* bad = nullptr;
+  ~TracksWork() {
+    void* all[] = {table, bad};
+    for (void* p : all)
+      if (p) (void)hipFree(p);
+  }
+};
+
+}  // namespace
+}  // namespace phmrf
+
+using namespace phmrf;
+
+extern "C" {
+
+int phmrf_state_tracks(const uint8_t* labels_dev, int H, int W, int diagonal, int64_t dist0, int K, int64_t d_min, int64_t d_max,
+                       int64_t* rows_host, int64_t* cols_host_or_null, void* hip_stream) {
+  PHMRF_CHECK(labels_dev && rows_host, PHMRF_ERR_INVALID, "NULL labels or rows");
+  PHMRF_CHECK(diagonal == 0 || diagonal == 1, PHMRF_ERR_INVALID, "diagonal must be 0 or 1");
+  PHMRF_CHECK(diagonal || cols_host_or_null, PHMRF_ERR_INVALID, "an off-diagonal block needs cols");
+  PHMRF_CHECK(H >= 1 && W >= 1, PHMRF_ERR_INVALID, "H and W must be >= 1");
+  PHMRF_CHECK(K >= 1, PHMRF_ERR_INVALID, "K must be >= 1");
+  PHMRF_CHECK(!diagonal || H == W, PHMRF_ERR_INVALID, "a diagonal block is square (H == W)");
+  PHMRF_CHECK(!diagonal || dist0 == 0, PHMRF_ERR_INVALID, "a diagonal block has dist0 == 0");
+  PHMRF_CHECK(d_min >= 0, PHMRF_ERR_INVALID, "d_min must be >= 0");
+  PHMRF_CHECK(d_max == -1 || d_max >= d_min, PHMRF_ERR_INVALID, "d_max must be >= d_min, or -1 for no upper limit");
+  PHMRF_CHECK(K <= 64, PHMRF_ERR_UNSUPPORTED, "K must be <= 64");
+  const int64_t n = grid_row_first<int64_t>(H, W, diagonal);
+  PHMRF_CHECK(n < ((int64_t)1 << 31) - 64, PHMRF_ERR_UNSUPPORTED, "n must be below 2^31 - 64");
+  PHMRF_CHECK(dist0 > -((int64_t)1 << 31) && dist0 < ((int64_t)1 << 31) &&
+                  (dist0 < 0 ? -dist0 : dist0) + H + W < ((int64_t)1 << 31),
+              PHMRF_ERR_UNSUPPORTED, "|dist0| + H + W must be below 2^31");
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  const size_t words = ((size_t)H + (diagonal ? 0 : (size_t)W)) * (size_t)K;
+  const int per_row = (W + TRACKS_TILE_W - 1) / TRACKS_TILE_W;
+  const int64_t ntiles = diagonal ? (int64_t)TRACKS_PER_SUPER * grid_row_first<int64_t>(per_row, per_row, 1)
+                                  : (int64_t)((H + TRACKS_TILE_H - 1) / TRACKS_TILE_H) * per_row;
+
+  TracksWork work;
+  PHMRF_TRY(alloc(&work.table, words));
+  PHMRF_TRY(alloc(&work.bad, 1));
+  PHMRF_HIP(hipMemsetAsync(work.table, 0, words * sizeof(unsigned), st));
+  PHMRF_HIP(hipMemsetAsync(work.bad, 0, sizeof(int), st));
+  // every distance is below INT_MAX: a d_min up there leaves nothing inside, a d_max up there is no limit
+  const int d_lo = d_min < INT_MAX ? (int)d_min : INT_MAX, d_hi = (d_max == -1 || d_max > INT_MAX) ? INT_MAX : (int)d_max;
+  hipLaunchKernelGGL(tracks_kernel, dim3(grid_of(ntiles, 1, TRACKS_GRID_CAP)), dim3(256), 0, st, labels_dev, H, W, diagonal,
+                     (int)dist0, K, d_lo, d_hi, per_row, ntiles, work.table, work.bad);
+  PHMRF_HIP(hipGetLastError());
+  int bad = 0;
+  PHMRF_HIP(hipMemcpyAsync(&bad, work.bad, sizeof(int), hipMemcpyDeviceToHost, st));
+  PHMRF_HIP(hipStreamSynchronize(st));
+  PHMRF_CHECK(!bad, PHMRF_ERR_INVALID, "a label inside the window is >= K");
+  std::vector<unsigned> got(words);
+  PHMRF_HIP(hipMemcpyAsync(got.data(), work.table, words * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  PHMRF_HIP(hipStreamSynchronize(st));
+  const size_t nrow = (size_t)H * (size_t)K;
+  for (size_t t = 0; t < nrow; ++t) rows_host[t] = (int64_t)got[t];
+  if (!diagonal)
+    for (size_t t = nrow; t < words; ++t) cols_host_or_null[t - nrow] = (int64_t)got[t];
+  return PHMRF_OK;
+}
+
+}  // extern "C"
