@@ -484,6 +484,39 @@ PHMRF_API int phmrf_state_tracks(const uint8_t* labels_dev, int H, int W, int di
                                  int64_t d_max /* -1: no upper limit */, int64_t* rows_host /* [H*K] */,
                                  int64_t* cols_host_or_null /* [W*K]; ignored for a diagonal block */, void* hip_stream);
 
+/* phmrf_pair_enrichment: the states of ONE region's bin pairs counted against the annotation of their two bins and against
+ * their exact genomic distance (no block, no ABI bump).  Labels in the node order of
+ * phmrf_smooth_labels.  Row bin i carries the class row_class[i] and column bin j the class col_class[j] (u8, < C; 0 stands
+ * for "unannotated"), and optionally the segments row_seg[i], col_seg[j] (int32, -1: none).  A diagonal block has one set
+ * of bins: its column pointers are ignored and the row arrays serve both.  For a stored node (i, j):
+ *   d = |dist0 + j - i| (dist0 = start_bin2 - start_bin1), INSIDE the window when d_min <= d and (d_max == -1 or d <= d_max),
+ *   as in phmrf_state_tracks;
+ *   pair category p = (row_class[i] C + col_class[j]) 2 + same, with same = 1 when segments are given, row_seg[i] >= 0 and
+ *   row_seg[i] == col_seg[j], else 0: P = 2 C C categories.
+ * Over the stored nodes inside the window, every node once (a diagonal block's mirror twins are not doubled:
+ * phmrf_label_contingency's convention):
+ *   obs_host          host int64 [P K]: the nodes of category p in state k
+ *   state_dist_host   host int64 [D K]: the nodes at the distance d_lo + t in state k
+ *   cat_dist_host     host int64 [D P]: the nodes at the distance d_lo + t of category p; this table depends on the geometry
+ *                     and the annotation alone, not on the labels
+ * so sum(obs) == sum(state_dist) == sum(cat_dist) == the nodes inside the window, the row sums of obs are the column sums
+ * of cat_dist and the column sums of obs those of state_dist.  The distances of the region that lie inside the window are
+ * one range; [d_lo, d_lo + D) must hold it (D may be 0 when no node is inside the window: then every table is zero).
+ * Nodes outside the window are never inspected: a label >= K or a class >= C there is no error and changes no count.
+ * Queued on hip_stream, returns when done.  Integers only: the same bytes from run to run.
+ * PHMRF_ERR_INVALID (nothing written) for a NULL labels_dev, row_class_dev or output table, a NULL col_class_dev_or_null on an
+ * off-diagonal block, one segment pointer without the other on an off-diagonal block, H < 1, W < 1, K < 1, C < 1, D < 0,
+ * d_lo < 0, a non-square diagonal block, a diagonal block with dist0 != 0, d_min < 0, d_max < d_min unless d_max is -1, a node
+ * inside the window whose label is >= K or one of whose two classes is >= C, or a table range that does not hold every
+ * distance inside the window; PHMRF_ERR_UNSUPPORTED for K > 64, C > 8, n >= 2^31 - 64, |dist0| + H + W >= 2^31 or
+ * D max(K, 2 C C) >= 2^31. */
+PHMRF_API int phmrf_pair_enrichment(const uint8_t* labels_dev, int H, int W, int diagonal, int64_t dist0, int K, int C,
+                                    const uint8_t* row_class_dev /* [H] */, const uint8_t* col_class_dev_or_null /* [W] */,
+                                    const int32_t* row_seg_dev_or_null /* [H] */, const int32_t* col_seg_dev_or_null /* [W] */,
+                                    int64_t d_min, int64_t d_max /* -1: no upper limit */, int64_t d_lo, int64_t D,
+                                    int64_t* obs_host /* [2*C*C*K] */, int64_t* state_dist_host /* [D*K] */,
+                                    int64_t* cat_dist_host /* [D*2*C*C] */, void* hip_stream);
+
 /* ---- profiling the states ------------------------------------------------------------------------- */
 /* What a state IS, from the block's resident f32 observations x (the uploaded float64 rounded to nearest) and its current
  * labels (no ABI bump: the calls only add entry points).  Both calls run over the nodes the block OWNS

@@ -142,6 +142,17 @@ def parse_args(argv=None):
     parser.add_option("--tracks_field", default="state_vec", help="--tracks: state_vec or state_vec_smooth")
     parser.add_option("--tracks_dist", default="0-", help="--tracks: at most 8 windows of genomic distance in bp, lo-hi or lo- "
                       "(no upper limit), separated by commas; the default 0- is every distance")
+    parser.add_option("--enrich", default="", help="skip loading data and fitting: count the states of this .mat between the "
+                      "annotated classes of --enrich_bed (pairs of bins by class pair, inside one interval or not) against an "
+                      "expectation matched by exact genomic distance; writes enrich_<stem>.npz and enrich_<stem>.txt under "
+                      "--output (--resolution gives the bin size)")
+    parser.add_option("--enrich_bed", default="", help="--enrich: the annotation, a text file of `chrom start stop name` lines "
+                      "with at most 7 distinct names")
+    parser.add_option("--enrich_field", default="state_vec", help="--enrich: state_vec or state_vec_smooth")
+    parser.add_option("--enrich_dist", default="0-", help="--enrich: ONE window of genomic distance in bp, lo-hi or lo- (no upper "
+                      "limit); the default 0- is every distance")
+    parser.add_option("--enrich_segments", default="0", help="--enrich: 1 = every line of --enrich_bed is a segment of its own "
+                      "(a TAD list): bin pairs inside one interval are counted apart from pairs across intervals")
     parser.add_option("-h", "--help", action="help")
     opts, _ = parser.parse_args(argv)
     return opts
@@ -372,6 +383,35 @@ def check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment,
         raise SystemExit("--tracks_dist: %s" % e)
 
 
+def check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments, resolution, segment, postprocess, compare,
+                 domains, render, tracks, ancestral, save_model, profile, filter_device):
+    """--enrich FILE.mat --enrich_bed FILE reads one finished state map and an annotation: it goes with nothing that loads data
+    or fits, and with no other reader of a state map -> the window (d_min, d_max) in bins, or None"""
+    if not enrich:
+        if enrich_bed:
+            raise SystemExit("--enrich and --enrich_bed go together: the .mat and its annotation file")
+        return None
+    if not enrich_bed:
+        raise SystemExit("--enrich and --enrich_bed go together: the .mat and its annotation file")
+    for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
+                        ("--render", render), ("--tracks", tracks), ("--ancestral", ancestral), ("--save_model", save_model),
+                        ("--profile 1", str(profile) == "1"), ("--filter_device 1", str(filter_device) == "1")):
+        if value:
+            raise SystemExit("--enrich cannot be combined with %s: it loads no data and fits nothing" % name)
+    if enrich_field not in ("state_vec", "state_vec_smooth"):
+        raise SystemExit("--enrich_field must be state_vec or state_vec_smooth, not %r" % (enrich_field,))
+    if str(enrich_segments) not in ("0", "1"):
+        raise SystemExit("--enrich_segments must be 0 or 1")
+    from phylo_hmrf_amd.tracks import parse_windows
+    try:
+        wins = parse_windows(enrich_dist, int(resolution))
+    except ValueError as e:
+        raise SystemExit("--enrich_dist: %s" % e)
+    if len(wins) != 1:
+        raise SystemExit("--enrich_dist takes one window lo-hi or lo-, not %d" % len(wins))
+    return wins[0]
+
+
 def run(num_states, chromvec, root_path, multiple, species_name, sort_states, run_id1, cons_param, method_mode,
         initial_mode, initial_weight, initial_weight1, initial_magnitude, position1, position2, filter_sigma, beta,
         beta1, num_neighbor, filter_mode, conv_threshold, estimate_type, simu_version, annotation, reload_mode,
@@ -382,7 +422,9 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
         compare_min_conf="0", compare_area="-1", profile="0", profile_quantiles="0.003,0.25,0.5,0.75,0.997",
         domains="", domains_field="state_vec", domains_area="-1", render="", render_field="state_vec", render_side="2048",
         render_colors="", render_outline="0", render_conf="0", render_mark="", tracks="", tracks_field="state_vec",
-        tracks_dist="0-"):
+        tracks_dist="0-", enrich="", enrich_bed="", enrich_field="state_vec", enrich_dist="0-", enrich_segments="0"):
+    check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments, resolution, segment, postprocess,
+                 compare or compare_with, domains, render, tracks, ancestral, save_model, profile, filter_device)
     check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment, postprocess, compare or compare_with, domains,
                  ancestral, save_model, profile, filter_device)
     side = check_render(render, render_field, render_side, render_outline, render_conf, segment, postprocess,
@@ -399,6 +441,12 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
     if filter_device and (int(reload_mode) == 1 or int(synthetic) > 0 or postprocess):
         raise SystemExit("--filter_device 1 runs the raw loader's filter on the GPU: it cannot be combined with --reload 1, "
                          "--synthetic or --postprocess, where nothing is filtered")
+    if enrich:
+        from phylo_hmrf_amd.enrich import enrich_files
+        out = enrich_files(enrich, enrich_bed, str(output_path), int(resolution), field=enrich_field, window_bp=enrich_dist,
+                           segments=str(enrich_segments) == "1")
+        print("enrichment written: %s" % out)
+        return out
     if tracks:
         from phylo_hmrf_amd.tracks import tracks_files
         out = tracks_files(tracks, str(output_path), int(resolution), field=tracks_field, windows_bp=tracks_dist)
@@ -607,4 +655,6 @@ if __name__ == "__main__":
         domains_field=opts.domains_field, domains_area=opts.domains_area, render=opts.render,
         render_field=opts.render_field, render_side=opts.render_side, render_colors=opts.render_colors,
         render_outline=opts.render_outline, render_conf=opts.render_conf, render_mark=opts.render_mark,
-        tracks=opts.tracks, tracks_field=opts.tracks_field, tracks_dist=opts.tracks_dist)
+        tracks=opts.tracks, tracks_field=opts.tracks_field, tracks_dist=opts.tracks_dist, enrich=opts.enrich,
+        enrich_bed=opts.enrich_bed, enrich_field=opts.enrich_field, enrich_dist=opts.enrich_dist,
+        enrich_segments=opts.enrich_segments)

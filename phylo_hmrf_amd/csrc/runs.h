@@ -1,6 +1,7 @@
-// What the post-processing's kernel files share (smooth.hip, compare.hip, profile.hip, domains.hip): the capped grid, the wave helpers of their integer
-// accumulations -- one atomic per RUN of equal destination among consecutive lanes, because state maps are piecewise
-// constant -- and the full-matrix area of a grid component.
+// What the post-processing's kernel files share (smooth.hip, compare.hip, profile.hip, domains.hip, tracks.hip, enrich.hip):
+// the capped grid, the wave helpers of their integer accumulations -- one atomic per RUN of equal destination among
+// consecutive lanes, because state maps are piecewise constant --, the split of a label row into aligned words (tracks.hip,
+// enrich.hip) and the full-matrix area of a grid component.
 #pragma once
 
 #include "common.h"
@@ -40,6 +41,28 @@ __device__ __forceinline__ void wave_run_add(T* dst, int key, T x) {
   const T before = __shfl(x, h > 0 ? h - 1 : 0, 64);
   const bool next_head = lane == 63 || ((heads >> (lane + 1)) & 1ull);
   if (key >= 0 && next_head) atomicAdd(dst + key, x - (h > 0 ? before : (T)0));
+}
+
+// The stored cells of storage row i of a label map between the columns j0 and j1 (a diagonal block: from the diagonal on):
+// columns [ja, ja + nc) at p; `head` bytes (at most three) up to the next 4-byte boundary of the address, nvec aligned words of
+// four labels, then the bytes from `tail` on: nbytes = head + what follows the words.  A region's slice of a state_vec starts at
+// any byte and a diagonal block's rows shift by one node each, so every row has its own head.
+struct LabelRow {
+  const uint8_t* p;
+  int ja, head, nvec, tail, nbytes;
+};
+
+__device__ __forceinline__ LabelRow label_row(const uint8_t* __restrict__ labels, int i, int j0, int j1, int W, int diagonal) {
+  LabelRow r;
+  r.ja = (diagonal && j0 < i) ? i : j0;
+  const int nc = j1 - r.ja;                            // >= 1 is the caller's business
+  r.p = labels + grid_id<int64_t>(i, r.ja, W, diagonal);
+  r.head = (int)((4 - (reinterpret_cast<uintptr_t>(r.p) & 3)) & 3);
+  if (r.head > nc) r.head = nc;
+  r.nvec = (nc - r.head) >> 2;
+  r.tail = r.head + 4 * r.nvec;
+  r.nbytes = r.head + (nc - r.tail);
+  return r;
 }
 
 // band of a distance d >= 0: 0 for d == 0, else t with 2^(t-1) <= d < 2^t (PHMRF_DIFF_BANDS of them below 2^31)

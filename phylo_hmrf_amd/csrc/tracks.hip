@@ -40,26 +40,6 @@ struct TracksTile {
   bool whole;
 };
 
-// the stored cells of row i of a tile: columns [ja, ja + nc) at p; `head` bytes (at most three) up to the next 4-byte boundary
-// of the address, nvec aligned words, then the bytes from `tail` on: nbytes = head + what follows the words
-struct TracksRow {
-  const uint8_t* p;
-  int ja, head, nvec, tail, nbytes;
-};
-
-__device__ __forceinline__ TracksRow tracks_row(const uint8_t* __restrict__ labels, const TracksTile& t, int i, int W, int diagonal) {
-  TracksRow r;
-  r.ja = (diagonal && t.j0 < i) ? i : t.j0;
-  const int nc = t.j1 - r.ja;                          // >= 1: a diagonal block's tile ends right of the diagonal
-  r.p = labels + grid_id<int64_t>(i, r.ja, W, diagonal);
-  r.head = (int)((4 - (reinterpret_cast<uintptr_t>(r.p) & 3)) & 3);
-  if (r.head > nc) r.head = nc;
-  r.nvec = (nc - r.head) >> 2;
-  r.tail = r.head + 4 * r.nvec;
-  r.nbytes = r.head + (nc - r.tail);
-  return r;
-}
-
 // tile T of the region; false for a tile of the last super-tile row's padding, and for a tile wholly outside the window
 // (the same answer for the whole workgroup)
 __device__ __forceinline__ bool tracks_tile(int64_t T, int H, int W, int diagonal, int per_row, int dist0, int d_lo, int d_hi,
@@ -118,7 +98,7 @@ __global__ __launch_bounds__(256) void tracks_kernel(const uint8_t* __restrict__
       word[u] = 0;
       single[u] = 0;
       if (i < t.i1) {                                                  // (everything but `lane` is the same for the wave)
-        const TracksRow r = tracks_row(labels, t, i, W, diagonal);
+        const LabelRow r = label_row(labels, i, t.j0, t.j1, W, diagonal);   // (nc >= 1: a diagonal block's tile ends right of the diagonal)
         if (lane < r.nvec) word[u] = *reinterpret_cast<const uint32_t*>(r.p + r.head + 4 * lane);
         if (lane < r.nbytes) single[u] = r.p[lane < r.head ? lane : r.tail + (lane - r.head)];
       }
@@ -127,7 +107,7 @@ __global__ __launch_bounds__(256) void tracks_kernel(const uint8_t* __restrict__
     for (int u = 0; u < TRACKS_ROWS_PER_WAVE; ++u) {
       const int i = t.i0 + wave + 4 * u;
       if (i >= t.i1) break;
-      const TracksRow r = tracks_row(labels, t, i, W, diagonal);
+      const LabelRow r = label_row(labels, i, t.j0, t.j1, W, diagonal);
       const int row_key = (i - t.i0) * TRACKS_STRIDE;
       const int x0 = dist0 - i;                                         // the cell's distance is |x0 + j|
       // one cell: -1 outside the window or with a label >= K, else the state; the column table takes it here
