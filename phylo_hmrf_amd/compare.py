@@ -17,26 +17,17 @@ import os
 
 import numpy as np
 
-from .smooth import MAX_STATES, check_len_vec, check_state_vec, default_max_area
+from .maps import (CONF_ONE, FIRST_CAPACITY, MAX_STATES, check_len_vec, check_state_vec, conf_array, default_max_area, device,
+                   list_rows, regions, stem)
 
 DIFF_BANDS = 32                  # include/phmrf.h PHMRF_DIFF_BANDS
 DOMAIN_COLS = 12                 # include/phmrf.h PHMRF_DOMAIN_COLS
-FIRST_CAPACITY = 65536           # domain rows of a region's first call; a second call takes the count the first returned
 CONTINGENCY_GRID_CAP = 1024      # csrc/compare.hip: workgroups of the contingency kernel ...
 CONTINGENCY_PER_TRIP = 1024      # ... and the nodes one of them reads per grid-stride trip
-CONF_ONE = float(1 << 24)        # the fixed point of the confidence sums
 
 
-def _device():
-    from . import _lib
-    import torch
-    lib = _lib.load()
-    _lib.require_gpu()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    return lib, dev, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _count(lib, stream, a_t, b_t, KA, KB):
+def count_pairs(lib, stream, a_t, b_t, KA, KB):
+    """-> int64 [KA, KB] of two uint8 device tensors of equal length (phmrf_label_contingency)"""
     from . import _lib
     C = np.zeros(KA * KB, dtype=np.int64)
     _lib.check(lib.phmrf_label_contingency(ctypes.c_void_p(a_t.data_ptr()), ctypes.c_void_p(b_t.data_ptr()), a_t.numel(), KA, KB,
@@ -52,12 +43,12 @@ def contingency(a, b, KA=None, KB=None):
         raise ValueError("the two maps have %d and %d nodes" % (a.size, b.size))
     KA = (int(a.max()) + 1 if a.size else 1) if KA is None else int(KA)
     KB = (int(b.max()) + 1 if b.size else 1) if KB is None else int(KB)
-    lib, dev, stream = _device()
+    lib, dev, stream = device()
     if a.size == 0:
         return np.zeros((KA, KB), dtype=np.int64)
     a_t = torch.from_numpy(a.astype(np.uint8)).to(dev)
     b_t = torch.from_numpy(b.astype(np.uint8)).to(dev)
-    return _count(lib, stream, a_t, b_t, KA, KB)
+    return count_pairs(lib, stream, a_t, b_t, KA, KB)
 
 
 def match_states(C):
@@ -107,13 +98,6 @@ def scores(C):
     return dict(agreement=float(np.trace(C) / n), ari=ari, nmi=float(nmi))
 
 
-def _conf(conf, n, what):
-    c = np.ascontiguousarray(np.asarray(conf, dtype=np.float32).reshape(-1))
-    if c.shape[0] != n:
-        raise ValueError("%s has %d entries for %d nodes" % (what, c.shape[0], n))
-    return c
-
-
 def compare_states(state_a, state_b, len_vec, conf_a=None, conf_b=None, match=False, min_conf=0.0, min_area=None):
     """Region by region -> dict:
       contingency [KA, K'], contingency_region [R, KA, K']   nodes per (state in A, state in B after map_b)
@@ -139,16 +123,16 @@ def compare_states(state_a, state_b, len_vec, conf_a=None, conf_b=None, match=Fa
         raise ValueError("min_area must be >= 1 (None: the smoothing's area rule + 1)")
     n, R = a.shape[0], L.shape[0]
     KA, KB = (int(a.max()) + 1 if n else 1), (int(b.max()) + 1 if n else 1)
-    lib, dev, stream = _device()
+    lib, dev, stream = device()
     a_t = torch.from_numpy(a.astype(np.uint8)).to(dev)
     b_t = torch.from_numpy(b.astype(np.uint8)).to(dev)
     ca_t = cb_t = None
     if conf_a is not None:
-        ca_t = torch.from_numpy(_conf(conf_a, n, "conf_a")).to(dev)
-        cb_t = torch.from_numpy(_conf(conf_b, n, "conf_b")).to(dev)
+        ca_t = torch.from_numpy(conf_array(conf_a, n, "conf_a")).to(dev)
+        cb_t = torch.from_numpy(conf_array(conf_b, n, "conf_b")).to(dev)
     diff_t = torch.zeros(n, dtype=torch.uint8, device=dev)
 
-    raw = np.stack([_count(lib, stream, a_t[int(r[1]):int(r[2])], b_t[int(r[1]):int(r[2])], KA, KB) for r in L])
+    raw = np.stack([count_pairs(lib, stream, a_t[lo:hi], b_t[lo:hi], KA, KB) for _, lo, hi, *_ in regions(L)])
     map_b = match_states(raw.sum(axis=0)) if match else np.arange(KB, dtype=np.uint8)
     per_region = permute_columns(raw, map_b)
     total = per_region.sum(axis=0)
@@ -156,25 +140,19 @@ def compare_states(state_a, state_b, len_vec, conf_a=None, conf_b=None, match=Fa
     bands = np.zeros((R, DIFF_BANDS, 3), dtype=np.int64)
     rows = []
     null = ctypes.c_void_p(None)
-    for r, row in enumerate(L):
-        lo, hi, H, W, diag = int(row[1]), int(row[2]), int(row[3]), int(row[4]), int(row[8])
+    for r, lo, hi, H, W, diag, dist0 in regions(L):
         area = default_max_area(H) + 1 if min_area is None else int(min_area)
 
-        def call(capacity):
-            table = np.zeros((max(capacity, 1), DOMAIN_COLS), dtype=np.int64)
-            found = ctypes.c_int64(0)
+        def call(capacity, table, found):
             _lib.check(lib.phmrf_diff_domains(
                 ctypes.c_void_p(a_t[lo:hi].data_ptr()), ctypes.c_void_p(b_t[lo:hi].data_ptr()),
                 map_b.ctypes.data_as(ctypes.c_void_p), null if ca_t is None else ctypes.c_void_p(ca_t[lo:hi].data_ptr()),
-                null if cb_t is None else ctypes.c_void_p(cb_t[lo:hi].data_ptr()), H, W, diag, int(row[6]) - int(row[5]), KA, KB,
+                null if cb_t is None else ctypes.c_void_p(cb_t[lo:hi].data_ptr()), H, W, diag, dist0, KA, KB,
                 min_conf, area, ctypes.c_void_p(diff_t[lo:hi].data_ptr()), capacity, _lib.ptr_i64(table), ctypes.byref(found),
                 _lib.ptr_i64(bands[r]), stream))
-            return table, int(found.value)
 
-        table, found = call(FIRST_CAPACITY)
-        if found > FIRST_CAPACITY:
-            table, found = call(found)
-        rows.append(np.concatenate([np.full((found, 1), r, dtype=np.int64), table[:found]], axis=1))
+        table = list_rows(call, DOMAIN_COLS, FIRST_CAPACITY)
+        rows.append(np.concatenate([np.full((table.shape[0], 1), r, dtype=np.int64), table], axis=1))
     domains = np.concatenate(rows) if rows else np.zeros((0, DOMAIN_COLS + 1), dtype=np.int64)
     if conf_a is None:
         domain_conf = np.full((domains.shape[0], 2), np.nan)
@@ -186,10 +164,6 @@ def compare_states(state_a, state_b, len_vec, conf_a=None, conf_b=None, match=Fa
                diff_vec=diff_t.cpu().numpy(), domains=domains, domain_conf=domain_conf)
     res.update(scores(total))
     return res
-
-
-def _stem(path):
-    return os.path.splitext(os.path.basename(path))[0]
 
 
 def domain_lines(domains, domain_conf, len_vec, resolution):
@@ -233,7 +207,7 @@ def compare_files(path_a, path_b, output_path, resolution, field="state_vec", ma
     sa, sb, L, (ca, cb) = load_pair(path_a, path_b, field, min_conf)
     res = compare_states(sa, sb, L, ca, cb, match=bool(match), min_conf=min_conf, min_area=min_area)
     os.makedirs(output_path, exist_ok=True)
-    name = "%s__%s" % (_stem(path_a), _stem(path_b))
+    name = "%s__%s" % (stem(path_a), stem(path_b))
     areas = np.array([default_max_area(r[3]) + 1 if min_area is None else int(min_area) for r in L], dtype=np.int64)
     out = os.path.join(output_path, "compare_%s.mat" % name)
     scipy.io.savemat(out, dict(res, len_vec=L, compare_field=field, compare_match=int(bool(match)),

@@ -9,14 +9,15 @@
 //   diff         diff[v] = 0 where a == map_b[b], else 2 where the node counts (both confidences >= min_conf) and 1 where
 //                it does not; the three counts per distance band |dist0 + j - i| in an LDS table per workgroup
 //   components   moves.hip's union-find on the diff map (launch_grid_components); the domains are the components of value 2,
-//                and they alone get smooth.hip's full-matrix area
-//   compact      roots of value 2 with area >= min_area get consecutive ids in node order (smooth_compact_kernel's scheme
-//                of a chunk of nodes per workgroup, with the workgroups' offsets from a scan) and are listed in that order
+//                and they alone get the full-matrix area (components_area_kernel over the nodes of value 2, components.h)
+//   compact      roots of value 2 with area >= min_area get consecutive ids in node order (components.h's count, scan and
+//                compact kernels: a chunk of nodes per workgroup, the workgroups' offsets from a scan) and are listed in that
+//                order
 //   stats        per node of a listed domain: bounding box by atomicMin / atomicMax, the two K-bin u64 state histograms
 //                and the two fixed-point confidence sums, one atomic per run of equal destination among consecutive lanes
 //   rows         per listed domain: its row of the table
 
-#include "runs.h"
+#include "components.h"
 
 #include <cstring>
 
@@ -124,106 +125,6 @@ __global__ __launch_bounds__(256) void compare_diff_kernel(const uint8_t* __rest
   if (threadIdx.x < PHMRF_DIFF_BANDS * 3 && tab[threadIdx.x]) atomicAdd(bands + threadIdx.x, (unsigned long long)tab[threadIdx.x]);
 }
 
-// smooth_area_kernel's rule for the nodes of value 2 alone: acc[root] += (weight << 32) | 1 per node (weight 1 on the
-// diagonal, 2 elsewhere), mirror[root] = 1 if j - i <= 1.  Two maps mostly agree, so the map's component of value 0 holds
-// nearly every node: counted too, every wave's atomic would land on its one root (61 % of a call's kernel time, measured).
-__global__ __launch_bounds__(256) void compare_area_kernel(const int32_t* __restrict__ comp, const uint8_t* __restrict__ diff,
-                                                           int64_t n, int W, int diagonal, unsigned long long* __restrict__ acc,
-                                                           uint8_t* __restrict__ mirror) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t base = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) - lane; base < n; base += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t v = base + lane;
-    int key = -1;
-    unsigned long long x = 0;
-    if (v < n && diff[v] == 2) {
-      int i, j;
-      grid_coords(v, W, diagonal, &i, &j);
-      key = comp[v];
-      x = ((unsigned long long)(diagonal && i == j ? 1 : 2) << 32) | 1ull;
-      if (diagonal && j - i <= 1) mirror[key] = 1;
-    }
-    if (__ballot(key >= 0) == 0ull) continue;           // (the same for the whole wave)
-    wave_run_add(acc, key, x);
-  }
-}
-
-__device__ __forceinline__ bool listed_root(int64_t v, const uint8_t* __restrict__ diff, int diagonal,
-                                            const unsigned long long* __restrict__ acc, const uint8_t* __restrict__ mirror,
-                                            long long min_area) {
-  return diff[v] == 2 && component_area(v, diagonal, acc, mirror) >= min_area;
-}
-
-// The listed domains get consecutive ids in ascending order of their roots, after smooth_compact_kernel's scheme: every
-// workgroup owns `chunk` consecutive nodes.  That kernel takes a workgroup's ids with an atomic, in whatever order the
-// workgroups arrive; here the order is part of the result, so the workgroups' counts are written out (count), summed in
-// workgroup order (scan) and the ids handed out from those offsets (compact).
-// per_group[g] = listed roots among workgroup g's nodes
-__global__ __launch_bounds__(256) void compare_count_kernel(const int32_t* __restrict__ comp, const uint8_t* __restrict__ diff,
-                                                            int64_t n, int64_t chunk, int diagonal,
-                                                            const unsigned long long* __restrict__ acc,
-                                                            const uint8_t* __restrict__ mirror, long long min_area,
-                                                            int* __restrict__ per_group) {
-  __shared__ int wave_cnt[4];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t start = (int64_t)blockIdx.x * chunk, end = start + chunk < n ? start + chunk : n;
-  int mine = 0;
-  for (int64_t v = start + threadIdx.x; v < end; v += 256)
-    mine += comp[v] == (int)v && listed_root(v, diff, diagonal, acc, mirror, min_area);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off, 64);
-  if (lane == 0) wave_cnt[wid] = mine;
-  __syncthreads();
-  if (threadIdx.x == 0) per_group[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-}
-
-// exclusive prefix sum of per_group[0 .. g) in place (g <= 4096: one workgroup), *count = the total
-__global__ __launch_bounds__(256) void compare_scan_kernel(int* __restrict__ per_group, int g, int* __restrict__ count) {
-  __shared__ int part[256];
-  const int per = (g + 255) / 256, lo = threadIdx.x * per, hi = lo + per < g ? lo + per : g;
-  int s = 0;
-  for (int t = lo; t < hi; ++t) s += per_group[t];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  int before = 0;
-  for (int t = 0; t < (int)threadIdx.x; ++t) before += part[t];
-  for (int t = lo; t < hi; ++t) {
-    const int c = per_group[t];
-    per_group[t] = before;
-    before += c;
-  }
-  if (threadIdx.x == 255) *count = before;
-}
-
-// cid[root] = id of a listed domain, -1 for any other root; roots[id] = root for id < cap
-__global__ __launch_bounds__(256) void compare_compact_kernel(const int32_t* __restrict__ comp, const uint8_t* __restrict__ diff,
-                                                              int64_t n, int64_t chunk, int diagonal,
-                                                              const unsigned long long* __restrict__ acc,
-                                                              const uint8_t* __restrict__ mirror, long long min_area,
-                                                              const int* __restrict__ per_group, int64_t cap,
-                                                              int32_t* __restrict__ cid, int32_t* __restrict__ roots) {
-  __shared__ int wave_cnt[4];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t start = (int64_t)blockIdx.x * chunk, end = start + chunk < n ? start + chunk : n;
-  int base = per_group[blockIdx.x];
-  for (int64_t b0 = start; b0 < end; b0 += 256) {
-    const int64_t v = b0 + threadIdx.x;
-    const bool root = v < end && comp[v] == (int)v;
-    const bool listed = root && listed_root(v, diff, diagonal, acc, mirror, min_area);
-    const unsigned long long mask = __ballot(listed);
-    __syncthreads();                                   // (wave_cnt of the previous trip has been read)
-    if (lane == 0) wave_cnt[wid] = __popcll(mask);
-    __syncthreads();
-    int off = base;
-    for (int w = 0; w < wid; ++w) off += wave_cnt[w];
-    if (root) {
-      const int id = listed ? off + __popcll(mask & (lanes_at_or_below(lane) >> 1)) : -1;
-      cid[v] = id;
-      if (id >= 0 && id < cap) roots[id] = (int32_t)v;
-    }
-    base += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-  }
-}
-
 // per node of a listed domain c < cap: box[4c ..] = min i, max i, min j, max j; hist_a[c KA + a], hist_b[c KM + map[b]],
 // sums[2c], sums[2c + 1] the fixed-point confidences
 __global__ __launch_bounds__(256) void compare_stats_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, MapB map,
@@ -248,11 +149,8 @@ __global__ __launch_bounds__(256) void compare_stats_kernel(const uint8_t* __res
     if (c >= 0) {
       int i, j;
       grid_coords(v, W, diagonal, &i, &j);
-      int* bx = box + 4 * (int64_t)c;
-      if (i < bx[0]) atomicMin(bx, i);                  // (a stale read only costs an atomic: the bounds move one way)
-      if (i > bx[1]) atomicMax(bx + 1, i);
-      if (j < bx[2]) atomicMin(bx + 2, j);
-      if (j > bx[3]) atomicMax(bx + 3, j);
+      widen(box + 4 * (int64_t)c, i, i);
+      widen(box + 4 * (int64_t)c + 2, j, j);
       ka = c * KA + a[v];
       kb = c * KM + map.to[b[v]];
       if (conf_a) {
@@ -267,17 +165,6 @@ __global__ __launch_bounds__(256) void compare_stats_kernel(const uint8_t* __res
       wave_run_add(sums, c >= 0 ? 2 * c + 1 : -1, fb);
     }
   }
-}
-
-__device__ __forceinline__ int mode_of(const unsigned long long* __restrict__ row, int K) {
-  unsigned long long best = 0;
-  int k = 0;
-  for (int q = 0; q < K; ++q)
-    if (row[q] > best) {                // strictly: the lowest state wins a tie
-      best = row[q];
-      k = q;
-    }
-  return k;
 }
 
 __global__ __launch_bounds__(256) void compare_rows_kernel(const int32_t* __restrict__ roots, int count, int diagonal,
@@ -297,44 +184,13 @@ __global__ __launch_bounds__(256) void compare_rows_kernel(const int32_t* __rest
     row[4] = box[4 * (int64_t)c + 3];
     row[5] = (long long)(acc[r] & 0xffffffffull);
     row[6] = component_area(r, diagonal, acc, mirror);
-    row[7] = mode_of(hist_a + (int64_t)c * KA, KA);
-    row[8] = mode_of(hist_b + (int64_t)c * KM, KM);
+    row[7] = mode_of(hist_a + (int64_t)c * KA, KA).state;
+    row[8] = mode_of(hist_b + (int64_t)c * KM, KM).state;
     row[9] = (long long)sums[2 * (int64_t)c];
     row[10] = (long long)sums[2 * (int64_t)c + 1];
     row[11] = 0;
   }
 }
-
-__global__ __launch_bounds__(256) void compare_box_init_kernel(int* __restrict__ box, int64_t count) {
-  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < count; c += (int64_t)gridDim.x * blockDim.x) {
-    box[4 * c] = box[4 * c + 2] = 0x7fffffff;
-    box[4 * c + 1] = box[4 * c + 3] = -1;
-  }
-}
-
-// device buffers of one call, released on every way out
-struct CompareWork {
-  uint8_t* diff = nullptr;
-  int32_t* comp = nullptr;
-  int32_t* cid = nullptr;
-  unsigned long long* acc = nullptr;
-  uint8_t* mirror = nullptr;
-  unsigned long long* bands = nullptr;
-  int* scalars = nullptr;          // [0] bad input, [1] number of listed domains
-  int* per_group = nullptr;
-  int32_t* roots = nullptr;
-  int* box = nullptr;
-  unsigned long long* hist_a = nullptr;
-  unsigned long long* hist_b = nullptr;
-  unsigned long long* sums = nullptr;
-  long long* table = nullptr;
-  unsigned long long* counts = nullptr;
-  ~CompareWork() {
-    void* all[] = {diff, comp, cid, acc, mirror, bands, scalars, per_group, roots, box, hist_a, hist_b, sums, table, counts};
-    for (void* p : all)
-      if (p) (void)hipFree(p);
-  }
-};
 
 }  // namespace
 }  // namespace phmrf
@@ -347,9 +203,8 @@ int phmrf_label_contingency(const uint8_t* a_dev, const uint8_t* b_dev, int64_t 
                             void* hip_stream) {
   PHMRF_CHECK(a_dev && b_dev && counts_host, PHMRF_ERR_INVALID, "NULL buffer");
   PHMRF_CHECK(n >= 0, PHMRF_ERR_INVALID, "n must be >= 0");
-  PHMRF_CHECK(KA >= 1 && KB >= 1, PHMRF_ERR_INVALID, "KA and KB must be >= 1");
-  PHMRF_CHECK(KA <= 64 && KB <= 64, PHMRF_ERR_UNSUPPORTED, "KA and KB must be <= 64");
-  PHMRF_CHECK(n < ((int64_t)1 << 31) - 64, PHMRF_ERR_UNSUPPORTED, "n must be below 2^31 - 64");
+  PHMRF_TRY(check_states(KA, KB, "KA and KB"));
+  PHMRF_TRY(check_nodes(n, "n must be below 2^31 - 64"));
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   const int nb = KA * KB;
   std::vector<unsigned long long> got((size_t)nb, 0ull);
@@ -360,17 +215,19 @@ int phmrf_label_contingency(const uint8_t* a_dev, const uint8_t* b_dev, int64_t 
     const bool together = ((reinterpret_cast<uintptr_t>(b_dev) + (uintptr_t)head) & 3) == 0;
     const int64_t nvec = together ? (n - head) / 4 : 0;
     if (!together) head = 0;
-    CompareWork w;
-    PHMRF_TRY(alloc(&w.counts, (size_t)nb));
-    PHMRF_TRY(alloc(&w.scalars, 1));
-    PHMRF_HIP(hipMemsetAsync(w.counts, 0, (size_t)nb * sizeof(unsigned long long), st));
-    PHMRF_HIP(hipMemsetAsync(w.scalars, 0, sizeof(int), st));
+    Buffers buf;
+    unsigned long long* counts;
+    int* flag;
+    PHMRF_TRY(buf.get(&counts, (size_t)nb));
+    PHMRF_TRY(buf.get(&flag, 1));
+    PHMRF_HIP(hipMemsetAsync(counts, 0, (size_t)nb * sizeof(unsigned long long), st));
+    PHMRF_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
     const int g = grid_of(n, CONT_PER_TRIP, CONT_GRID_CAP);
-    hipLaunchKernelGGL(contingency_kernel, dim3(g), dim3(256), 0, st, a_dev, b_dev, n, head, nvec, KA, KB, w.counts, w.scalars);
+    hipLaunchKernelGGL(contingency_kernel, dim3(g), dim3(256), 0, st, a_dev, b_dev, n, head, nvec, KA, KB, counts, flag);
     PHMRF_HIP(hipGetLastError());
     int bad = 0;
-    PHMRF_HIP(hipMemcpyAsync(&bad, w.scalars, sizeof(int), hipMemcpyDeviceToHost, st));
-    PHMRF_HIP(hipMemcpyAsync(got.data(), w.counts, (size_t)nb * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    PHMRF_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    PHMRF_HIP(hipMemcpyAsync(got.data(), counts, (size_t)nb * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     PHMRF_HIP(hipStreamSynchronize(st));
     PHMRF_CHECK(!bad, PHMRF_ERR_INVALID, "a label is >= K");
   }
@@ -386,20 +243,16 @@ int phmrf_diff_domains(const uint8_t* a_dev, const uint8_t* b_dev, const uint8_t
   PHMRF_CHECK(a_dev && b_dev && n_domains, PHMRF_ERR_INVALID, "NULL buffer");
   PHMRF_CHECK((conf_a_dev_or_null == nullptr) == (conf_b_dev_or_null == nullptr), PHMRF_ERR_INVALID,
               "give both confidences or neither");
-  PHMRF_CHECK(H >= 1 && W >= 1, PHMRF_ERR_INVALID, "H and W must be >= 1");
-  PHMRF_CHECK(diagonal == 0 || diagonal == 1, PHMRF_ERR_INVALID, "diagonal must be 0 or 1");
-  PHMRF_CHECK(!diagonal || H == W, PHMRF_ERR_INVALID, "a diagonal block is square (H == W)");
-  PHMRF_CHECK(KA >= 1 && KB >= 1, PHMRF_ERR_INVALID, "KA and KB must be >= 1");
-  PHMRF_CHECK(KA <= 64 && KB <= 64, PHMRF_ERR_UNSUPPORTED, "KA and KB must be <= 64");
+  int64_t n;
+  PHMRF_TRY(check_region(H, W, diagonal, &n));
+  PHMRF_TRY(check_states(KA, KB, "KA and KB"));
   PHMRF_CHECK(capacity >= 0, PHMRF_ERR_INVALID, "capacity must be >= 0");
   PHMRF_CHECK(min_area >= 1, PHMRF_ERR_INVALID, "min_area must be >= 1");
   PHMRF_CHECK(capacity == 0 || table_host, PHMRF_ERR_INVALID, "a table is needed when capacity > 0");
   uint32_t mc_bits;
   std::memcpy(&mc_bits, &min_conf, sizeof(mc_bits));
   PHMRF_CHECK((mc_bits & 0x7fffffffu) <= 0x7f800000u, PHMRF_ERR_INVALID, "min_conf is not a number");
-  const int64_t reach = (dist0 < 0 ? -dist0 : dist0) + (H > W ? H : W);
-  PHMRF_CHECK(dist0 > -((int64_t)1 << 31) && reach < ((int64_t)1 << 31), PHMRF_ERR_INVALID,
-              "a distance |dist0 + j - i| of 2^31 or more has no band");
+  PHMRF_TRY(check_reach(dist0, H, W));
   MapB map;
   int KM = KB;
   for (int k = 0; k < 64; ++k) map.to[k] = (uint8_t)k;
@@ -411,71 +264,80 @@ int phmrf_diff_domains(const uint8_t* a_dev, const uint8_t* b_dev, const uint8_t
       if (map.to[k] + 1 > KM) KM = map.to[k] + 1;
     }
   }
-  const int64_t n = diagonal ? (int64_t)W * (W + 1) / 2 : (int64_t)H * W;
-  PHMRF_CHECK(n < ((int64_t)1 << 31) - 64, PHMRF_ERR_UNSUPPORTED, "the region must have fewer than 2^31 - 64 nodes");
+  PHMRF_TRY(check_nodes(n));
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   const int g = grid_of(n);
   const int64_t chunk = ((n + g - 1) / g + 255) / 256 * 256;     // compact: consecutive nodes per workgroup
 
-  CompareWork w;
-  PHMRF_TRY(alloc(&w.scalars, 2));
-  PHMRF_TRY(alloc(&w.bands, (size_t)PHMRF_DIFF_BANDS * 3));
-  PHMRF_TRY(alloc(&w.diff, (size_t)n));
-  PHMRF_HIP(hipMemsetAsync(w.scalars, 0, 2 * sizeof(int), st));
-  PHMRF_HIP(hipMemsetAsync(w.bands, 0, (size_t)PHMRF_DIFF_BANDS * 3 * sizeof(unsigned long long), st));
+  Buffers buf;
+  int* scalars;                    // [0] bad input, [1] number of listed domains
+  unsigned long long* bands_dev;
+  uint8_t* diff;
+  PHMRF_TRY(buf.get(&scalars, 2));
+  PHMRF_TRY(buf.get(&bands_dev, (size_t)PHMRF_DIFF_BANDS * 3));
+  PHMRF_TRY(buf.get(&diff, (size_t)n));
+  PHMRF_HIP(hipMemsetAsync(scalars, 0, 2 * sizeof(int), st));
+  PHMRF_HIP(hipMemsetAsync(bands_dev, 0, (size_t)PHMRF_DIFF_BANDS * 3 * sizeof(unsigned long long), st));
   hipLaunchKernelGGL(compare_diff_kernel, dim3(g), dim3(256), 0, st, a_dev, b_dev, map, conf_a_dev_or_null, conf_b_dev_or_null,
-                     n, W, diagonal, (long long)dist0, KA, KB, min_conf, w.diff, w.bands, w.scalars);
+                     n, W, diagonal, (long long)dist0, KA, KB, min_conf, diff, bands_dev, scalars);
   PHMRF_HIP(hipGetLastError());
   int bad = 0;
-  PHMRF_HIP(hipMemcpyAsync(&bad, w.scalars, sizeof(int), hipMemcpyDeviceToHost, st));
+  PHMRF_HIP(hipMemcpyAsync(&bad, scalars, sizeof(int), hipMemcpyDeviceToHost, st));
   PHMRF_HIP(hipStreamSynchronize(st));
   PHMRF_CHECK(!(bad & 1), PHMRF_ERR_INVALID, "a label is >= K");
   PHMRF_CHECK(!(bad & 2), PHMRF_ERR_INVALID, "a confidence is not a finite number in [0, 1]");
 
-  PHMRF_TRY(alloc(&w.comp, (size_t)n));
-  PHMRF_TRY(alloc(&w.cid, (size_t)n));
-  PHMRF_TRY(alloc(&w.acc, (size_t)n));
-  PHMRF_TRY(alloc(&w.mirror, (size_t)n));
-  PHMRF_TRY(alloc(&w.per_group, (size_t)g));
-  PHMRF_TRY(launch_grid_components(w.comp, n, W, diagonal, w.diff, st));
-  PHMRF_HIP(hipMemsetAsync(w.acc, 0, (size_t)n * sizeof(unsigned long long), st));
-  PHMRF_HIP(hipMemsetAsync(w.mirror, 0, (size_t)n, st));
-  hipLaunchKernelGGL(compare_area_kernel, dim3(g), dim3(256), 0, st, w.comp, w.diff, n, W, diagonal, w.acc, w.mirror);
-  hipLaunchKernelGGL(compare_count_kernel, dim3(g), dim3(256), 0, st, w.comp, w.diff, n, chunk, diagonal, w.acc, w.mirror,
-                     (long long)min_area, w.per_group);
-  hipLaunchKernelGGL(compare_scan_kernel, dim3(1), dim3(256), 0, st, w.per_group, g, w.scalars + 1);
+  int32_t *comp, *cid;
+  unsigned long long* acc;
+  uint8_t* mirror;
+  int* per_group;
+  PHMRF_TRY(buf.get(&comp, (size_t)n));
+  PHMRF_TRY(buf.get(&cid, (size_t)n));
+  PHMRF_TRY(buf.get(&acc, (size_t)n));
+  PHMRF_TRY(buf.get(&mirror, (size_t)n));
+  PHMRF_TRY(buf.get(&per_group, (size_t)g));
+  const ListedRoot is_listed = {diff, diagonal, acc, mirror, (long long)min_area, ANY_AREA};
+  PHMRF_TRY(launch_grid_components(comp, n, W, diagonal, diff, st));
+  PHMRF_HIP(hipMemsetAsync(acc, 0, (size_t)n * sizeof(unsigned long long), st));
+  PHMRF_HIP(hipMemsetAsync(mirror, 0, (size_t)n, st));
+  hipLaunchKernelGGL(components_area_kernel<DiffNode>, dim3(g), dim3(256), 0, st, comp, DiffNode{diff}, n, W, diagonal, acc, mirror);
+  hipLaunchKernelGGL(components_count_kernel, dim3(g), dim3(256), 0, st, comp, n, chunk, is_listed, per_group);
+  hipLaunchKernelGGL(components_scan_kernel, dim3(1), dim3(256), 0, st, per_group, g, scalars + 1);
   PHMRF_HIP(hipGetLastError());
   int count = 0;
-  PHMRF_HIP(hipMemcpyAsync(&count, w.scalars + 1, sizeof(int), hipMemcpyDeviceToHost, st));
+  PHMRF_HIP(hipMemcpyAsync(&count, scalars + 1, sizeof(int), hipMemcpyDeviceToHost, st));
   PHMRF_HIP(hipStreamSynchronize(st));
   const int64_t listed = count < capacity ? count : capacity;
   PHMRF_CHECK(listed * (KA > KM ? KA : KM) < ((int64_t)1 << 31), PHMRF_ERR_UNSUPPORTED,
               "domains x states must stay below 2^31: ask for fewer rows");
   std::vector<long long> rows((size_t)listed * PHMRF_DOMAIN_COLS);
   if (listed > 0) {
-    PHMRF_TRY(alloc(&w.roots, (size_t)listed));
-    PHMRF_TRY(alloc(&w.box, (size_t)listed * 4));
-    PHMRF_TRY(alloc(&w.hist_a, (size_t)listed * KA));
-    PHMRF_TRY(alloc(&w.hist_b, (size_t)listed * KM));
-    PHMRF_TRY(alloc(&w.sums, (size_t)listed * 2));
-    PHMRF_TRY(alloc(&w.table, rows.size()));
-    PHMRF_HIP(hipMemsetAsync(w.hist_a, 0, (size_t)listed * KA * sizeof(unsigned long long), st));
-    PHMRF_HIP(hipMemsetAsync(w.hist_b, 0, (size_t)listed * KM * sizeof(unsigned long long), st));
-    PHMRF_HIP(hipMemsetAsync(w.sums, 0, (size_t)listed * 2 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(compare_box_init_kernel, dim3(grid_of(listed)), dim3(256), 0, st, w.box, listed);
-    hipLaunchKernelGGL(compare_compact_kernel, dim3(g), dim3(256), 0, st, w.comp, w.diff, n, chunk, diagonal, w.acc, w.mirror,
-                       (long long)min_area, w.per_group, listed, w.cid, w.roots);
+    int32_t* roots;
+    int* box;
+    unsigned long long *hist_a, *hist_b, *sums;
+    long long* table;
+    PHMRF_TRY(buf.get(&roots, (size_t)listed));
+    PHMRF_TRY(buf.get(&box, (size_t)listed * 4));
+    PHMRF_TRY(buf.get(&hist_a, (size_t)listed * KA));
+    PHMRF_TRY(buf.get(&hist_b, (size_t)listed * KM));
+    PHMRF_TRY(buf.get(&sums, (size_t)listed * 2));
+    PHMRF_TRY(buf.get(&table, rows.size()));
+    PHMRF_HIP(hipMemsetAsync(hist_a, 0, (size_t)listed * KA * sizeof(unsigned long long), st));
+    PHMRF_HIP(hipMemsetAsync(hist_b, 0, (size_t)listed * KM * sizeof(unsigned long long), st));
+    PHMRF_HIP(hipMemsetAsync(sums, 0, (size_t)listed * 2 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(components_bounds_init_kernel, dim3(grid_of(listed)), dim3(256), 0, st, box, 2 * listed);
+    hipLaunchKernelGGL(components_compact_kernel, dim3(g), dim3(256), 0, st, comp, n, chunk, is_listed, per_group, listed, cid,
+                       roots);
     hipLaunchKernelGGL(compare_stats_kernel, dim3(g), dim3(256), 0, st, a_dev, b_dev, map, conf_a_dev_or_null,
-                       conf_b_dev_or_null, w.diff, w.comp, w.cid, n, W, diagonal, KA, KM, listed, w.box, w.hist_a, w.hist_b,
-                       w.sums);
-    hipLaunchKernelGGL(compare_rows_kernel, dim3(grid_of(listed)), dim3(256), 0, st, w.roots, (int)listed, diagonal, w.acc,
-                       w.mirror, w.box, w.hist_a, w.hist_b, w.sums, KA, KM, w.table);
+                       conf_b_dev_or_null, diff, comp, cid, n, W, diagonal, KA, KM, listed, box, hist_a, hist_b, sums);
+    hipLaunchKernelGGL(compare_rows_kernel, dim3(grid_of(listed)), dim3(256), 0, st, roots, (int)listed, diagonal, acc, mirror,
+                       box, hist_a, hist_b, sums, KA, KM, table);
     PHMRF_HIP(hipGetLastError());
-    PHMRF_HIP(hipMemcpyAsync(rows.data(), w.table, rows.size() * sizeof(long long), hipMemcpyDeviceToHost, st));
+    PHMRF_HIP(hipMemcpyAsync(rows.data(), table, rows.size() * sizeof(long long), hipMemcpyDeviceToHost, st));
   }
   unsigned long long bands[PHMRF_DIFF_BANDS * 3];
-  PHMRF_HIP(hipMemcpyAsync(bands, w.bands, sizeof(bands), hipMemcpyDeviceToHost, st));
-  if (diff_out_dev_or_null) PHMRF_HIP(hipMemcpyAsync(diff_out_dev_or_null, w.diff, (size_t)n, hipMemcpyDeviceToDevice, st));
+  PHMRF_HIP(hipMemcpyAsync(bands, bands_dev, sizeof(bands), hipMemcpyDeviceToHost, st));
+  if (diff_out_dev_or_null) PHMRF_HIP(hipMemcpyAsync(diff_out_dev_or_null, diff, (size_t)n, hipMemcpyDeviceToDevice, st));
   PHMRF_HIP(hipStreamSynchronize(st));
   for (size_t t = 0; t < rows.size(); ++t) table_host[t] = (int64_t)rows[t];
   if (band_counts_host_or_null)

@@ -5,23 +5,23 @@
 //                every node looks at its four forward neighbours; each workgroup keeps a K x K table of u32 bins in LDS (at
 //                most 16 KB), ONE LDS atomic per run of equal (a, b) among consecutive lanes (wave_run_add), and flushes
 //                its non-zero bins with u64 global atomics.  The call folds the table into the symmetric one on the host.
-//   check        a label >= K, a confidence that is not a finite number in [0, 1]
+//   check        a label >= K, a confidence that is not a finite number in [0, 1] (components_check_kernel)
 //   components   moves.hip's union-find on the map itself (launch_grid_components)
-//   areas        smooth_area_kernel's rule, every node counted.  A state map always has components of millions of nodes, and
-//                one atomic per wave and trip on such a root serialises (compare_area_kernel: 61 % of that call's kernel
-//                time).  So a wave owns a SEGMENT of consecutive nodes and CARRIES one root in its registers: the lanes on
+//   areas        components_area_kernel's rule, every node counted.  A state map always has components of
+//                millions of nodes, and one atomic per wave and trip on such a root serialises (components_area_kernel: 61 %
+//                of a comparison's kernel time when it counted the nodes of value 0).  So a wave owns a SEGMENT of consecutive nodes and CARRIES one root in its registers: the lanes on
 //                that root add to a sum of their own, which goes out with one atomic when a trip of 64 nodes holds no node of
 //                the carried root (the wave then carries the root of the trip's last node) and at the segment's end.  Nodes
 //                of any other root go one atomic per run of equal root.
 //   count        per workgroup's chunk of nodes: the listed roots (area >= min_area); per state: all roots
-//   scan/compact compare.hip's scheme: ids in ascending order of the roots
+//   scan/compact components.h's kernels: ids in ascending order of the roots
 //   stats        per node of a listed domain with id < capacity: bounding box and distance range (atomicMin / atomicMax
 //                behind a plain read), the fixed-point confidence sum, and per stored neighbour of another state one count in
 //                the domain's K-bin histogram.  The same carry: box, range and sum of the carried domain in the lanes'
 //                registers, its histogram in K LDS bins of the wave; other domains one atomic per run.
 //   rows         per listed domain: its row of the table
 
-#include "runs.h"
+#include "components.h"
 
 namespace phmrf {
 namespace {
@@ -64,17 +64,6 @@ __global__ __launch_bounds__(256) void adjacency_kernel(const uint8_t* __restric
   __syncthreads();
   for (int t = threadIdx.x; t < nb; t += 256)
     if (bins[t]) atomicAdd(counts + t, (unsigned long long)bins[t]);
-}
-
-// bad |= 1 for a label >= K, 2 for a confidence that is not a finite number in [0, 1]
-__global__ __launch_bounds__(256) void domains_check_kernel(const uint8_t* __restrict__ labels, const float* __restrict__ conf,
-                                                            int64_t n, int K, int* __restrict__ bad) {
-  int wrong = 0;
-  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (int64_t)gridDim.x * blockDim.x) {
-    if ((int)labels[v] >= K) wrong |= 1;
-    if (conf && !unit_conf(conf[v])) wrong |= 2;
-  }
-  if (wrong) atomicOr(bad, wrong);
 }
 
 // the nodes [*lo, *hi) of this wave: `seg` (a multiple of 64) consecutive nodes per wave, in wave order
@@ -124,95 +113,19 @@ __global__ __launch_bounds__(256) void domains_area_kernel(const int32_t* __rest
   if (carried >= 0) wave_add(acc + carried, mine);
 }
 
-__device__ __forceinline__ bool listed_root(int64_t v, int diagonal, const unsigned long long* __restrict__ acc,
-                                            const uint8_t* __restrict__ mirror, long long min_area) {
-  return component_area(v, diagonal, acc, mirror) >= min_area;
-}
-
 // per_group[g] = listed roots among workgroup g's `chunk` consecutive nodes; ncomp[k] += its roots of state k, listed or not
 __global__ __launch_bounds__(256) void domains_count_kernel(const int32_t* __restrict__ comp, const uint8_t* __restrict__ labels,
-                                                            int64_t n, int64_t chunk, int diagonal,
-                                                            const unsigned long long* __restrict__ acc,
-                                                            const uint8_t* __restrict__ mirror, long long min_area, int K,
+                                                            int64_t n, int64_t chunk, ListedRoot listed, int K,
                                                             int* __restrict__ per_group, unsigned long long* __restrict__ ncomp) {
   __shared__ int wave_cnt[4];
   __shared__ unsigned of_state[64];
   if (threadIdx.x < 64) of_state[threadIdx.x] = 0;
   __syncthreads();
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t start = (int64_t)blockIdx.x * chunk, end = start + chunk < n ? start + chunk : n;
-  int mine = 0;
-  for (int64_t v = start + threadIdx.x; v < end; v += 256)
-    if (comp[v] == (int)v) {
-      mine += listed_root(v, diagonal, acc, mirror, min_area);
-      atomicAdd(of_state + labels[v], 1u);
-    }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off, 64);
-  if (lane == 0) wave_cnt[wid] = mine;
-  __syncthreads();
-  if (threadIdx.x == 0) per_group[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+  int64_t start, end;
+  group_chunk(n, chunk, &start, &end);
+  const int total = count_listed(comp, start, end, listed, wave_cnt, [&](int64_t v) { atomicAdd(of_state + labels[v], 1u); });
+  if (threadIdx.x == 0) per_group[blockIdx.x] = total;
   if ((int)threadIdx.x < K && of_state[threadIdx.x]) atomicAdd(ncomp + threadIdx.x, (unsigned long long)of_state[threadIdx.x]);
-}
-
-// exclusive prefix sum of per_group[0 .. g) in place (g <= DOM_GRID_CAP: one workgroup), *count = the total
-__global__ __launch_bounds__(256) void domains_scan_kernel(int* __restrict__ per_group, int g, int* __restrict__ count) {
-  __shared__ int part[256];
-  const int per = (g + 255) / 256, lo = threadIdx.x * per, hi = lo + per < g ? lo + per : g;
-  int s = 0;
-  for (int t = lo; t < hi; ++t) s += per_group[t];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  int before = 0;
-  for (int t = 0; t < (int)threadIdx.x; ++t) before += part[t];
-  for (int t = lo; t < hi; ++t) {
-    const int c = per_group[t];
-    per_group[t] = before;
-    before += c;
-  }
-  if (threadIdx.x == 255) *count = before;
-}
-
-// cid[root] = id of a listed domain, -1 for any other root; roots[id] = root for id < cap
-__global__ __launch_bounds__(256) void domains_compact_kernel(const int32_t* __restrict__ comp, int64_t n, int64_t chunk,
-                                                              int diagonal, const unsigned long long* __restrict__ acc,
-                                                              const uint8_t* __restrict__ mirror, long long min_area,
-                                                              const int* __restrict__ per_group, int64_t cap,
-                                                              int32_t* __restrict__ cid, int32_t* __restrict__ roots) {
-  __shared__ int wave_cnt[4];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t start = (int64_t)blockIdx.x * chunk, end = start + chunk < n ? start + chunk : n;
-  int base = per_group[blockIdx.x];
-  for (int64_t b0 = start; b0 < end; b0 += 256) {
-    const int64_t v = b0 + threadIdx.x;
-    const bool root = v < end && comp[v] == (int)v;
-    const bool listed = root && listed_root(v, diagonal, acc, mirror, min_area);
-    const unsigned long long mask = __ballot(listed);
-    __syncthreads();                                   // (wave_cnt of the previous trip has been read)
-    if (lane == 0) wave_cnt[wid] = __popcll(mask);
-    __syncthreads();
-    int off = base;
-    for (int w = 0; w < wid; ++w) off += wave_cnt[w];
-    if (root) {
-      const int id = listed ? off + __popcll(mask & (lanes_at_or_below(lane) >> 1)) : -1;
-      cid[v] = id;
-      if (id >= 0 && id < cap) roots[id] = (int32_t)v;
-    }
-    base += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-  }
-}
-
-__global__ __launch_bounds__(256) void domains_ext_init_kernel(int* __restrict__ ext, int64_t count) {
-  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < count; c += (int64_t)gridDim.x * blockDim.x) {
-    ext[DOM_EXT * c] = ext[DOM_EXT * c + 2] = ext[DOM_EXT * c + 4] = 0x7fffffff;
-    ext[DOM_EXT * c + 1] = ext[DOM_EXT * c + 3] = ext[DOM_EXT * c + 5] = -1;
-  }
-}
-
-// e[0] = min(e[0], lo), e[1] = max(e[1], hi)  (a stale read only costs an atomic: the bounds move one way)
-__device__ __forceinline__ void widen(int* __restrict__ e, int lo, int hi) {
-  if (lo < e[0]) atomicMin(e, lo);
-  if (hi > e[1]) atomicMax(e + 1, hi);
 }
 
 __device__ __forceinline__ int wave_min(int x) {
@@ -352,16 +265,7 @@ __global__ __launch_bounds__(256) void domains_rows_kernel(const int32_t* __rest
     const int64_t r = roots[c];
     long long* row = table + (int64_t)c * PHMRF_STATE_DOMAIN_COLS;
     const int* e = ext + DOM_EXT * (int64_t)c;
-    unsigned long long total = 0, best = 0;
-    int towards = -1;
-    for (int q = 0; q < K; ++q) {
-      const unsigned long long h = hist[(int64_t)c * K + q];
-      total += h;
-      if (h > best) {                   // strictly: the lowest state wins a tie
-        best = h;
-        towards = q;
-      }
-    }
+    const Mode m = mode_of(hist + (int64_t)c * K, K);
     row[0] = r;
     row[1] = e[0];
     row[2] = e[1];
@@ -370,47 +274,14 @@ __global__ __launch_bounds__(256) void domains_rows_kernel(const int32_t* __rest
     row[5] = (long long)(acc[r] & 0xffffffffull);
     row[6] = component_area(r, diagonal, acc, mirror);
     row[7] = labels[r];
-    row[8] = (long long)total;
-    row[9] = towards;
-    row[10] = (long long)best;
+    row[8] = (long long)m.total;
+    row[9] = m.best ? m.state : -1;      // (borders no other state)
+    row[10] = (long long)m.best;
     row[11] = e[4];
     row[12] = e[5];
     row[13] = (long long)sums[c];
     row[14] = row[15] = 0;
   }
-}
-
-// device buffers of one call, released on every way out
-struct DomainsWork {
-  int32_t* comp = nullptr;
-  int32_t* cid = nullptr;
-  unsigned long long* acc = nullptr;
-  uint8_t* mirror = nullptr;
-  int* scalars = nullptr;          // [0] bad input, [1] number of listed domains
-  int* per_group = nullptr;
-  unsigned long long* ncomp = nullptr;
-  int32_t* roots = nullptr;
-  int* ext = nullptr;
-  unsigned long long* hist = nullptr;
-  unsigned long long* sums = nullptr;
-  long long* table = nullptr;
-  unsigned long long* counts = nullptr;
-  ~DomainsWork() {
-    void* all[] = {comp, cid, acc, mirror, scalars, per_group, ncomp, roots, ext, hist, sums, table, counts};
-    for (void* p : all)
-      if (p) (void)hipFree(p);
-  }
-};
-
-int check_region(int H, int W, int diagonal, int K, int64_t* n) {
-  PHMRF_CHECK(H >= 1 && W >= 1, PHMRF_ERR_INVALID, "H and W must be >= 1");
-  PHMRF_CHECK(diagonal == 0 || diagonal == 1, PHMRF_ERR_INVALID, "diagonal must be 0 or 1");
-  PHMRF_CHECK(!diagonal || H == W, PHMRF_ERR_INVALID, "a diagonal block is square (H == W)");
-  PHMRF_CHECK(K >= 1, PHMRF_ERR_INVALID, "K must be >= 1");
-  PHMRF_CHECK(K <= 64, PHMRF_ERR_UNSUPPORTED, "K must be <= 64");
-  *n = diagonal ? (int64_t)W * (W + 1) / 2 : (int64_t)H * W;
-  PHMRF_CHECK(*n < ((int64_t)1 << 31) - 64, PHMRF_ERR_UNSUPPORTED, "the region must have fewer than 2^31 - 64 nodes");
-  return PHMRF_OK;
 }
 
 }  // namespace
@@ -423,21 +294,25 @@ extern "C" {
 int phmrf_state_adjacency(const uint8_t* labels_dev, int H, int W, int diagonal, int K, int64_t* adj_host, void* hip_stream) {
   PHMRF_CHECK(labels_dev && adj_host, PHMRF_ERR_INVALID, "NULL buffer");
   int64_t n;
-  PHMRF_TRY(check_region(H, W, diagonal, K, &n));
+  PHMRF_TRY(check_region(H, W, diagonal, &n));
+  PHMRF_TRY(check_states(K));
+  PHMRF_TRY(check_nodes(n));
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   const int nb = K * K;
   std::vector<unsigned long long> got((size_t)nb, 0ull);
-  DomainsWork w;
-  PHMRF_TRY(alloc(&w.counts, (size_t)nb));
-  PHMRF_TRY(alloc(&w.scalars, 1));
-  PHMRF_HIP(hipMemsetAsync(w.counts, 0, (size_t)nb * sizeof(unsigned long long), st));
-  PHMRF_HIP(hipMemsetAsync(w.scalars, 0, sizeof(int), st));
+  Buffers buf;
+  unsigned long long* counts;
+  int* flag;
+  PHMRF_TRY(buf.get(&counts, (size_t)nb));
+  PHMRF_TRY(buf.get(&flag, 1));
+  PHMRF_HIP(hipMemsetAsync(counts, 0, (size_t)nb * sizeof(unsigned long long), st));
+  PHMRF_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
   hipLaunchKernelGGL(adjacency_kernel, dim3(grid_of(n, 256, DOM_GRID_CAP)), dim3(256), 0, st, labels_dev, n, H, W, diagonal, K,
-                     w.counts, w.scalars);
+                     counts, flag);
   PHMRF_HIP(hipGetLastError());
   int bad = 0;
-  PHMRF_HIP(hipMemcpyAsync(&bad, w.scalars, sizeof(int), hipMemcpyDeviceToHost, st));
-  PHMRF_HIP(hipMemcpyAsync(got.data(), w.counts, (size_t)nb * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  PHMRF_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+  PHMRF_HIP(hipMemcpyAsync(got.data(), counts, (size_t)nb * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   PHMRF_HIP(hipStreamSynchronize(st));
   PHMRF_CHECK(!bad, PHMRF_ERR_INVALID, "a label is >= K");
   // an edge was counted at (state of its first node, state of its second): both orders fold into the symmetric table
@@ -452,74 +327,85 @@ int phmrf_state_domains(const uint8_t* labels_dev, const float* conf_dev_or_null
                         int64_t* n_domains, int64_t* n_components_host_or_null, void* hip_stream) {
   PHMRF_CHECK(labels_dev && n_domains, PHMRF_ERR_INVALID, "NULL buffer");
   int64_t n;
-  PHMRF_TRY(check_region(H, W, diagonal, K, &n));
+  PHMRF_TRY(check_region(H, W, diagonal, &n));
+  PHMRF_TRY(check_states(K));
+  PHMRF_TRY(check_nodes(n));
   PHMRF_CHECK(capacity >= 0, PHMRF_ERR_INVALID, "capacity must be >= 0");
   PHMRF_CHECK(min_area >= 1, PHMRF_ERR_INVALID, "min_area must be >= 1");
   PHMRF_CHECK(capacity == 0 || table_host, PHMRF_ERR_INVALID, "a table is needed when capacity > 0");
-  const int64_t reach = (dist0 < 0 ? -dist0 : dist0) + (H > W ? H : W);
-  PHMRF_CHECK(dist0 > -((int64_t)1 << 31) && reach < ((int64_t)1 << 31), PHMRF_ERR_INVALID,
-              "a distance |dist0 + j - i| of 2^31 or more");
+  PHMRF_TRY(check_reach(dist0, H, W, ""));
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   const int g = grid_of(n, 256, DOM_GRID_CAP);
   const int64_t seg = ((n + 4 * (int64_t)g - 1) / (4 * (int64_t)g) + 63) / 64 * 64;      // areas, stats: nodes per wave
   const int64_t chunk = ((n + g - 1) / g + 255) / 256 * 256;                              // compact: nodes per workgroup
 
-  DomainsWork w;
-  PHMRF_TRY(alloc(&w.scalars, 2));
-  PHMRF_HIP(hipMemsetAsync(w.scalars, 0, 2 * sizeof(int), st));
-  hipLaunchKernelGGL(domains_check_kernel, dim3(g), dim3(256), 0, st, labels_dev, conf_dev_or_null, n, K, w.scalars);
+  Buffers buf;
+  int* scalars;                    // [0] bad input, [1] number of listed domains
+  PHMRF_TRY(buf.get(&scalars, 2));
+  PHMRF_HIP(hipMemsetAsync(scalars, 0, 2 * sizeof(int), st));
+  hipLaunchKernelGGL(components_check_kernel, dim3(g), dim3(256), 0, st, labels_dev, conf_dev_or_null, n, K, scalars);
   PHMRF_HIP(hipGetLastError());
   int bad = 0;
-  PHMRF_HIP(hipMemcpyAsync(&bad, w.scalars, sizeof(int), hipMemcpyDeviceToHost, st));
+  PHMRF_HIP(hipMemcpyAsync(&bad, scalars, sizeof(int), hipMemcpyDeviceToHost, st));
   PHMRF_HIP(hipStreamSynchronize(st));
   PHMRF_CHECK(!(bad & 1), PHMRF_ERR_INVALID, "a label is >= K");
   PHMRF_CHECK(!(bad & 2), PHMRF_ERR_INVALID, "a confidence is not a finite number in [0, 1]");
 
-  PHMRF_TRY(alloc(&w.comp, (size_t)n));
-  PHMRF_TRY(alloc(&w.cid, (size_t)n));
-  PHMRF_TRY(alloc(&w.acc, (size_t)n));
-  PHMRF_TRY(alloc(&w.mirror, (size_t)n));
-  PHMRF_TRY(alloc(&w.per_group, (size_t)g));
-  PHMRF_TRY(alloc(&w.ncomp, 64));
-  PHMRF_TRY(launch_grid_components(w.comp, n, W, diagonal, labels_dev, st));
-  PHMRF_HIP(hipMemsetAsync(w.acc, 0, (size_t)n * sizeof(unsigned long long), st));
-  PHMRF_HIP(hipMemsetAsync(w.mirror, 0, (size_t)n, st));
-  PHMRF_HIP(hipMemsetAsync(w.ncomp, 0, 64 * sizeof(unsigned long long), st));
-  hipLaunchKernelGGL(domains_area_kernel, dim3(g), dim3(256), 0, st, w.comp, n, seg, W, diagonal, w.acc, w.mirror);
-  hipLaunchKernelGGL(domains_count_kernel, dim3(g), dim3(256), 0, st, w.comp, labels_dev, n, chunk, diagonal, w.acc, w.mirror,
-                     (long long)min_area, K, w.per_group, w.ncomp);
-  hipLaunchKernelGGL(domains_scan_kernel, dim3(1), dim3(256), 0, st, w.per_group, g, w.scalars + 1);
+  int32_t *comp, *cid;
+  unsigned long long *acc, *ncomp_dev;
+  uint8_t* mirror;
+  int* per_group;
+  PHMRF_TRY(buf.get(&comp, (size_t)n));
+  PHMRF_TRY(buf.get(&cid, (size_t)n));
+  PHMRF_TRY(buf.get(&acc, (size_t)n));
+  PHMRF_TRY(buf.get(&mirror, (size_t)n));
+  PHMRF_TRY(buf.get(&per_group, (size_t)g));
+  PHMRF_TRY(buf.get(&ncomp_dev, 64));
+  const ListedRoot is_listed = {nullptr, diagonal, acc, mirror, (long long)min_area, ANY_AREA};
+  PHMRF_TRY(launch_grid_components(comp, n, W, diagonal, labels_dev, st));
+  PHMRF_HIP(hipMemsetAsync(acc, 0, (size_t)n * sizeof(unsigned long long), st));
+  PHMRF_HIP(hipMemsetAsync(mirror, 0, (size_t)n, st));
+  PHMRF_HIP(hipMemsetAsync(ncomp_dev, 0, 64 * sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(domains_area_kernel, dim3(g), dim3(256), 0, st, comp, n, seg, W, diagonal, acc, mirror);
+  hipLaunchKernelGGL(domains_count_kernel, dim3(g), dim3(256), 0, st, comp, labels_dev, n, chunk, is_listed, K, per_group,
+                     ncomp_dev);
+  hipLaunchKernelGGL(components_scan_kernel, dim3(1), dim3(256), 0, st, per_group, g, scalars + 1);
   PHMRF_HIP(hipGetLastError());
   int count = 0;
-  PHMRF_HIP(hipMemcpyAsync(&count, w.scalars + 1, sizeof(int), hipMemcpyDeviceToHost, st));
+  PHMRF_HIP(hipMemcpyAsync(&count, scalars + 1, sizeof(int), hipMemcpyDeviceToHost, st));
   PHMRF_HIP(hipStreamSynchronize(st));
   const int64_t listed = count < capacity ? count : capacity;
   PHMRF_CHECK(listed * K < ((int64_t)1 << 31), PHMRF_ERR_UNSUPPORTED, "domains x states must stay below 2^31: ask for fewer rows");
   std::vector<long long> rows((size_t)listed * PHMRF_STATE_DOMAIN_COLS);
   unsigned long long ncomp[64];
   if (listed > 0 || domain_out_dev_or_null) {
-    PHMRF_TRY(alloc(&w.roots, (size_t)listed));
-    PHMRF_TRY(alloc(&w.ext, (size_t)listed * DOM_EXT));
-    PHMRF_TRY(alloc(&w.hist, (size_t)listed * K));
-    PHMRF_TRY(alloc(&w.sums, (size_t)listed));
-    PHMRF_TRY(alloc(&w.table, rows.size()));
+    int32_t* roots;
+    int* ext;
+    unsigned long long *hist, *sums;
+    long long* table;
+    PHMRF_TRY(buf.get(&roots, (size_t)listed));
+    PHMRF_TRY(buf.get(&ext, (size_t)listed * DOM_EXT));
+    PHMRF_TRY(buf.get(&hist, (size_t)listed * K));
+    PHMRF_TRY(buf.get(&sums, (size_t)listed));
+    PHMRF_TRY(buf.get(&table, rows.size()));
     if (listed > 0) {
-      PHMRF_HIP(hipMemsetAsync(w.hist, 0, (size_t)listed * K * sizeof(unsigned long long), st));
-      PHMRF_HIP(hipMemsetAsync(w.sums, 0, (size_t)listed * sizeof(unsigned long long), st));
-      hipLaunchKernelGGL(domains_ext_init_kernel, dim3(grid_of(listed, 256, DOM_GRID_CAP)), dim3(256), 0, st, w.ext, listed);
+      PHMRF_HIP(hipMemsetAsync(hist, 0, (size_t)listed * K * sizeof(unsigned long long), st));
+      PHMRF_HIP(hipMemsetAsync(sums, 0, (size_t)listed * sizeof(unsigned long long), st));
+      hipLaunchKernelGGL(components_bounds_init_kernel, dim3(grid_of(listed, 256, DOM_GRID_CAP)), dim3(256), 0, st, ext,
+                         (DOM_EXT / 2) * listed);
     }
-    hipLaunchKernelGGL(domains_compact_kernel, dim3(g), dim3(256), 0, st, w.comp, n, chunk, diagonal, w.acc, w.mirror,
-                       (long long)min_area, w.per_group, listed, w.cid, w.roots);
-    hipLaunchKernelGGL(domains_stats_kernel, dim3(g), dim3(256), 0, st, labels_dev, conf_dev_or_null, w.comp, w.cid, n, seg, H, W,
-                       diagonal, (long long)dist0, K, listed, domain_out_dev_or_null, w.ext, w.hist, w.sums);
+    hipLaunchKernelGGL(components_compact_kernel, dim3(g), dim3(256), 0, st, comp, n, chunk, is_listed, per_group, listed, cid,
+                       roots);
+    hipLaunchKernelGGL(domains_stats_kernel, dim3(g), dim3(256), 0, st, labels_dev, conf_dev_or_null, comp, cid, n, seg, H, W,
+                       diagonal, (long long)dist0, K, listed, domain_out_dev_or_null, ext, hist, sums);
     if (listed > 0) {
-      hipLaunchKernelGGL(domains_rows_kernel, dim3(grid_of(listed, 256, DOM_GRID_CAP)), dim3(256), 0, st, w.roots, (int)listed,
-                         diagonal, K, labels_dev, w.acc, w.mirror, w.ext, w.hist, w.sums, w.table);
-      PHMRF_HIP(hipMemcpyAsync(rows.data(), w.table, rows.size() * sizeof(long long), hipMemcpyDeviceToHost, st));
+      hipLaunchKernelGGL(domains_rows_kernel, dim3(grid_of(listed, 256, DOM_GRID_CAP)), dim3(256), 0, st, roots, (int)listed,
+                         diagonal, K, labels_dev, acc, mirror, ext, hist, sums, table);
+      PHMRF_HIP(hipMemcpyAsync(rows.data(), table, rows.size() * sizeof(long long), hipMemcpyDeviceToHost, st));
     }
     PHMRF_HIP(hipGetLastError());
   }
-  PHMRF_HIP(hipMemcpyAsync(ncomp, w.ncomp, sizeof(ncomp), hipMemcpyDeviceToHost, st));
+  PHMRF_HIP(hipMemcpyAsync(ncomp, ncomp_dev, sizeof(ncomp), hipMemcpyDeviceToHost, st));
   PHMRF_HIP(hipStreamSynchronize(st));
   for (size_t t = 0; t < rows.size(); ++t) table_host[t] = (int64_t)rows[t];
   if (n_components_host_or_null)

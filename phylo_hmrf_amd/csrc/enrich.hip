@@ -50,48 +50,6 @@ inline size_t enrich_lds_bytes(int K, int C) {
   return 8 * (size_t)(ENRICH_TILE_W + ENRICH_TILE_H) + 4 * ((size_t)2 * C * C * K + (size_t)ENRICH_TILE_D * enrich_dist_stride(K));
 }
 
-// rows [i0, i1) and columns [j0, j1) of the storage; whole: every cell is inside the window; the cells' distances lie in
-// [near, near + nd)
-struct EnrichTile {
-  int i0, i1, j0, j1, near, nd;
-  bool whole;
-};
-
-// tile T of the region; false for a tile of the last super-tile row's padding, and for a tile wholly outside the window
-// (the same answer for the whole workgroup)
-__device__ __forceinline__ bool enrich_tile(int64_t T, int H, int W, int diagonal, int per_row, int dist0, int d_lo, int d_hi,
-                                            EnrichTile* t) {
-  int ti, tj;
-  if (diagonal) {                                      // the upper triangle of the per_row x per_row grid of super-tiles
-    int g;
-    grid_coords(T / ENRICH_PER_SUPER, per_row, 1, &g, &tj);
-    ti = g * ENRICH_PER_SUPER + (int)(T % ENRICH_PER_SUPER);
-  } else {
-    grid_coords(T, per_row, 0, &ti, &tj);
-  }
-  const int64_t i0 = (int64_t)ti * ENRICH_TILE_H;
-  if (i0 >= H) return false;
-  int64_t j0 = (int64_t)tj * ENRICH_TILE_W;
-  const int64_t i1 = i0 + ENRICH_TILE_H < H ? i0 + ENRICH_TILE_H : H;
-  const int64_t j1 = j0 + ENRICH_TILE_W < W ? j0 + ENRICH_TILE_W : W;
-  t->i0 = (int)i0;
-  t->i1 = (int)i1;
-  t->j0 = (int)j0;
-  t->j1 = (int)j1;
-  if (diagonal && j0 < i0) j0 = i0;                    // the stored cells of the tile start at the diagonal
-  if (j0 >= j1) return false;
-  // the range of dist0 + j - i over the tile (|dist0| + H + W < 2^31: an int holds every distance)
-  const int x_lo = dist0 + (int)j0 - ((int)i1 - 1), x_hi = dist0 + ((int)j1 - 1) - (int)i0;
-  const int a_lo = x_lo < 0 ? -x_lo : x_lo, a_hi = x_hi < 0 ? -x_hi : x_hi;
-  const int far = a_lo > a_hi ? a_lo : a_hi;
-  const int near = (x_lo <= 0 && x_hi >= 0) ? 0 : (a_lo < a_hi ? a_lo : a_hi);
-  if (far < d_lo || near > d_hi) return false;
-  t->whole = near >= d_lo && far <= d_hi;
-  t->near = near;
-  t->nd = far - near + 1;                              // <= x_hi - x_lo + 1 <= ENRICH_TILE_D
-  return true;
-}
-
 // obs: u64 [2 C C][K]; state_dist: u32 [D][K], row 0 the distance tab_lo; d_hi: INT_MAX for no upper limit.  col_class /
 // col_seg: the row arrays again for a diagonal block; row_seg and col_seg both null without segments.
 __global__ __launch_bounds__(256) void enrich_label_kernel(const uint8_t* __restrict__ labels, int H, int W, int diagonal, int dist0,
@@ -113,8 +71,8 @@ __global__ __launch_bounds__(256) void enrich_label_kernel(const uint8_t* __rest
   const int rot = (l32 >> 3) & 3;
   int wrong = 0;
   for (int64_t T = blockIdx.x; T < ntiles; T += gridDim.x) {
-    EnrichTile t;
-    if (!enrich_tile(T, H, W, diagonal, per_row, dist0, d_lo, d_hi, &t)) continue;
+    WindowTile t;                                      // (its distances: nd <= ENRICH_TILE_D)
+    if (!window_tile<ENRICH_TILE_H, ENRICH_TILE_W>(T, H, W, diagonal, per_row, dist0, d_lo, d_hi, &t)) continue;
     // the half-wave's rows i0 + 2 wave + half, + 8, ...: every load of the tile is issued before the first count
     uint32_t word[ENRICH_PAIRS_PER_WAVE];
     int single[ENRICH_PAIRS_PER_WAVE];
@@ -256,15 +214,6 @@ __global__ __launch_bounds__(256) void enrich_class_kernel(int H, int W, int dia
   if (wrong) atomicOr(bad, BAD_CLASS);
 }
 
-// the device buffer of one call, released on every way out: obs u64 [P K] | state_dist u32 [D K] | cat_dist u32 [D P] | the flag
-// word -- one allocation and one memset, whatever the call's size
-struct EnrichWork {
-  unsigned long long* all = nullptr;
-  ~EnrichWork() {
-    if (all) (void)hipFree(all);
-  }
-};
-
 }  // namespace
 }  // namespace phmrf
 
@@ -292,7 +241,7 @@ int phmrf_pair_enrichment(const uint8_t* labels_dev, int H, int W, int diagonal,
   PHMRF_CHECK(K <= 64, PHMRF_ERR_UNSUPPORTED, "K must be <= 64");
   PHMRF_CHECK(C <= ENRICH_MAX_CLASSES, PHMRF_ERR_UNSUPPORTED, "C must be <= 8");
   const int64_t n = grid_row_first<int64_t>(H, W, diagonal);
-  PHMRF_CHECK(n < ((int64_t)1 << 31) - 64, PHMRF_ERR_UNSUPPORTED, "n must be below 2^31 - 64");
+  PHMRF_TRY(check_nodes(n, "n must be below 2^31 - 64"));
   PHMRF_CHECK(dist0 > -((int64_t)1 << 31) && dist0 < ((int64_t)1 << 31) &&
                   (dist0 < 0 ? -dist0 : dist0) + H + W < ((int64_t)1 << 31),
               PHMRF_ERR_UNSUPPORTED, "|dist0| + H + W must be below 2^31");
@@ -328,16 +277,18 @@ int phmrf_pair_enrichment(const uint8_t* labels_dev, int H, int W, int diagonal,
   const int slots = ((H < W ? H : W) + ENRICH_CHUNK - 1) / ENRICH_CHUNK;
   const int64_t nitems = (na + nb) * slots;
 
-  EnrichWork work;
+  // one allocation and one memset, whatever the call's size: obs u64 [P K] | state_dist u32 [D K] | cat_dist u32 [D P] | the flag word
+  Buffers buf;
+  unsigned long long* all;
   const size_t n_u32 = n_sd + n_cd + 1;
-  PHMRF_TRY(alloc(&work.all, n_obs + (n_u32 + 1) / 2));
-  unsigned* const state_dist = reinterpret_cast<unsigned*>(work.all + n_obs);
+  PHMRF_TRY(buf.get(&all, n_obs + (n_u32 + 1) / 2));
+  unsigned* const state_dist = reinterpret_cast<unsigned*>(all + n_obs);
   unsigned* const cat_dist = state_dist + n_sd;
   int* const flag = reinterpret_cast<int*>(cat_dist + n_cd);
-  PHMRF_HIP(hipMemsetAsync(work.all, 0, (n_obs + (n_u32 + 1) / 2) * sizeof(unsigned long long), st));
+  PHMRF_HIP(hipMemsetAsync(all, 0, (n_obs + (n_u32 + 1) / 2) * sizeof(unsigned long long), st));
   hipLaunchKernelGGL(enrich_label_kernel, dim3(grid_of(ntiles, 1, ENRICH_GRID_CAP)), dim3(256), enrich_lds_bytes(K, C), st, labels_dev,
                      H, W, diagonal, (int)dist0, K, C, row_class_dev, col_class, row_seg_dev_or_null, col_seg, (int)w_lo, (int)w_hi,
-                     (int)d_lo, per_row, ntiles, work.all, state_dist, flag);
+                     (int)d_lo, per_row, ntiles, all, state_dist, flag);
   PHMRF_HIP(hipGetLastError());
   hipLaunchKernelGGL(enrich_class_kernel, dim3(grid_of(nitems, 4, ENRICH_GRID_CAP)), dim3(256), 0, st, H, W, diagonal, (int)dist0, C,
                      row_class_dev, col_class, row_seg_dev_or_null, col_seg, (int)xa, (int)na, (int)xb, slots, nitems, (int)d_lo,
@@ -349,7 +300,7 @@ int phmrf_pair_enrichment(const uint8_t* labels_dev, int H, int W, int diagonal,
   PHMRF_CHECK(!(bad & BAD_LABEL), PHMRF_ERR_INVALID, "a label inside the window is >= K");
   PHMRF_CHECK(!(bad & BAD_CLASS), PHMRF_ERR_INVALID, "a class of a node inside the window is >= C");
   std::vector<unsigned long long> got(n_obs + (n_sd + n_cd + 1) / 2);          // the three tables in one copy
-  PHMRF_HIP(hipMemcpyAsync(got.data(), work.all, n_obs * sizeof(unsigned long long) + (n_sd + n_cd) * sizeof(unsigned),
+  PHMRF_HIP(hipMemcpyAsync(got.data(), all, n_obs * sizeof(unsigned long long) + (n_sd + n_cd) * sizeof(unsigned),
                            hipMemcpyDeviceToHost, st));
   PHMRF_HIP(hipStreamSynchronize(st));
   const unsigned* const got_u32 = reinterpret_cast<const unsigned*>(got.data() + n_obs);

@@ -24,25 +24,10 @@
 #include <algorithm>
 #include <cmath>
 
-#include "common.h"
+#include "runs.h"
 
 namespace phmrf {
 namespace {
-
-// device buffers of one call, released on every way out
-struct FilterWork {
-  double* a = nullptr;
-  double* b = nullptr;
-  ~FilterWork() {
-    if (a) (void)hipFree(a);
-    if (b) (void)hipFree(b);
-  }
-};
-
-int alloc_d(double** p, size_t count) {
-  PHMRF_HIP(hipMalloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(double)));
-  return PHMRF_OK;
-}
 
 // the launches below tile the plane with 64-column workgroups and stride over the rows
 constexpr int ROWS_PER_WG = 4;
@@ -310,13 +295,14 @@ int phmrf_filter_bilateral(const double* img_dev, double* out_dev, int64_t H, in
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   const int64_t n = H * W;
 
-  FilterWork w;                      // a: min / max partials, then the colour table; b: the spatial table
+  Buffers buf;
+  double *lut_a, *lut_b;             // a: min / max partials, then the colour table; b: the spatial table
   const int g = (int)std::min<int64_t>(1024, (n + 255) / 256);
-  PHMRF_TRY(alloc_d(&w.a, std::max<size_t>((size_t)2 * g, (size_t)bins)));
-  hipLaunchKernelGGL(minmax_kernel, dim3(g), dim3(256), 0, st, img_dev, n, w.a);
+  PHMRF_TRY(buf.get(&lut_a, std::max<size_t>((size_t)2 * g, (size_t)bins)));
+  hipLaunchKernelGGL(minmax_kernel, dim3(g), dim3(256), 0, st, img_dev, n, lut_a);
   PHMRF_HIP(hipGetLastError());
   std::vector<double> part((size_t)2 * g);
-  PHMRF_HIP(hipMemcpyAsync(part.data(), w.a, part.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  PHMRF_HIP(hipMemcpyAsync(part.data(), lut_a, part.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   PHMRF_HIP(hipStreamSynchronize(st));
   double mn = part[0], mx = part[1];
   for (int b = 1; b < g; ++b) {
@@ -344,9 +330,9 @@ int phmrf_filter_bilateral(const double* img_dev, double* out_dev, int64_t H, in
       range_lut[(size_t)kr * win_size + kc] = std::exp(-0.5 * d * d);
     }
   const double dist_scale = (double)bins / mx;
-  PHMRF_TRY(alloc_d(&w.b, range_lut.size()));
-  PHMRF_HIP(hipMemcpyAsync(w.a, color_lut.data(), color_lut.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  PHMRF_HIP(hipMemcpyAsync(w.b, range_lut.data(), range_lut.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  PHMRF_TRY(buf.get(&lut_b, range_lut.size()));
+  PHMRF_HIP(hipMemcpyAsync(lut_a, color_lut.data(), color_lut.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  PHMRF_HIP(hipMemcpyAsync(lut_b, range_lut.data(), range_lut.size() * sizeof(double), hipMemcpyHostToDevice, st));
 
   // LDS: the tile first, the colour table beside it when both fit
   const size_t pitch = (size_t)BL_TILE + win_size - 1;
@@ -359,13 +345,13 @@ int phmrf_filter_bilateral(const double* img_dev, double* out_dev, int64_t H, in
 #endif
   const size_t lds = (tile_lds ? tile_bytes : 0) + (lut_lds ? lut_bytes : 0);
   if (tile_lds && lut_lds)
-    PHMRF_TRY((launch_bilateral<true, true>(img_dev, out_dev, (int)H, (int)W, win_size, bins, dist_scale, w.b, w.a, lds, st)));
+    PHMRF_TRY((launch_bilateral<true, true>(img_dev, out_dev, (int)H, (int)W, win_size, bins, dist_scale, lut_b, lut_a, lds, st)));
   else if (tile_lds)
-    PHMRF_TRY((launch_bilateral<true, false>(img_dev, out_dev, (int)H, (int)W, win_size, bins, dist_scale, w.b, w.a, lds, st)));
+    PHMRF_TRY((launch_bilateral<true, false>(img_dev, out_dev, (int)H, (int)W, win_size, bins, dist_scale, lut_b, lut_a, lds, st)));
   else if (lut_lds)
-    PHMRF_TRY((launch_bilateral<false, true>(img_dev, out_dev, (int)H, (int)W, win_size, bins, dist_scale, w.b, w.a, lds, st)));
+    PHMRF_TRY((launch_bilateral<false, true>(img_dev, out_dev, (int)H, (int)W, win_size, bins, dist_scale, lut_b, lut_a, lds, st)));
   else
-    PHMRF_TRY((launch_bilateral<false, false>(img_dev, out_dev, (int)H, (int)W, win_size, bins, dist_scale, w.b, w.a, lds, st)));
+    PHMRF_TRY((launch_bilateral<false, false>(img_dev, out_dev, (int)H, (int)W, win_size, bins, dist_scale, lut_b, lut_a, lds, st)));
   PHMRF_HIP(hipStreamSynchronize(st));
   return PHMRF_OK;
 }
@@ -389,12 +375,13 @@ int phmrf_filter_gaussian(const double* img_dev, double* out_dev, double* tmp_de
     sum += weights[(size_t)(x + radius)];
   }
   for (double& v : weights) v /= sum;
-  FilterWork w;
-  PHMRF_TRY(alloc_d(&w.a, weights.size()));
-  PHMRF_HIP(hipMemcpyAsync(w.a, weights.data(), weights.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  Buffers buf;
+  double* weights_dev;
+  PHMRF_TRY(buf.get(&weights_dev, weights.size()));
+  PHMRF_HIP(hipMemcpyAsync(weights_dev, weights.data(), weights.size() * sizeof(double), hipMemcpyHostToDevice, st));
   const dim3 grid = plane_grid(H, W), tb(64, ROWS_PER_WG);
-  hipLaunchKernelGGL(gaussian_pass_kernel<0>, grid, tb, 0, st, img_dev, tmp_dev, (int)H, (int)W, radius, w.a);
-  hipLaunchKernelGGL(gaussian_pass_kernel<1>, grid, tb, 0, st, tmp_dev, out_dev, (int)H, (int)W, radius, w.a);
+  hipLaunchKernelGGL(gaussian_pass_kernel<0>, grid, tb, 0, st, img_dev, tmp_dev, (int)H, (int)W, radius, weights_dev);
+  hipLaunchKernelGGL(gaussian_pass_kernel<1>, grid, tb, 0, st, tmp_dev, out_dev, (int)H, (int)W, radius, weights_dev);
   PHMRF_HIP(hipGetLastError());
   PHMRF_HIP(hipStreamSynchronize(st));
   return PHMRF_OK;

@@ -166,20 +166,6 @@ __global__ __launch_bounds__(256) void state_moments_reduce_kernel(const double*
   if (threadIdx.x == 0) out[t] = part[0];
 }
 
-// device buffers of one call, released on every way out
-struct ProfileWork {
-  uint32_t* prefix = nullptr;
-  unsigned long long* hist = nullptr;
-  double* partial = nullptr;
-  double* sums = nullptr;
-  unsigned long long* counts = nullptr;      // [K] counts, then [K * 32] bands
-  ~ProfileWork() {
-    void* all[] = {prefix, hist, partial, sums, counts};
-    for (void* p : all)
-      if (p) (void)hipFree(p);
-  }
-};
-
 int owned_range(const phmrf_block* b, int64_t* first, int64_t* last) {
   PHMRF_CHECK(b->has_X, PHMRF_ERR_STATE, "observations not set");
   PHMRF_CHECK(b->has_labels, PHMRF_ERR_STATE, "labels not set (phmrf_block_set_labels or a solve)");
@@ -205,20 +191,22 @@ int phmrf_state_hist(phmrf_block_t b, int shift, int J, const uint32_t* prefix, 
   PHMRF_TRY(owned_range(b, &first, &last));
   const int K = b->K, S = b->S;
   const size_t slots = (size_t)K * S * J, nbins = slots * 256;
-  ProfileWork w;
-  PHMRF_TRY(alloc(&w.prefix, slots));
-  PHMRF_TRY(alloc(&w.hist, nbins));
-  if (shift != 24) PHMRF_HIP(hipMemcpyAsync(w.prefix, prefix, slots * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
-  PHMRF_HIP(hipMemsetAsync(w.hist, 0, nbins * sizeof(unsigned long long), b->stream));
+  Buffers buf;
+  uint32_t* prefix_dev;
+  unsigned long long* hist_dev;
+  PHMRF_TRY(buf.get(&prefix_dev, slots));
+  PHMRF_TRY(buf.get(&hist_dev, nbins));
+  if (shift != 24) PHMRF_HIP(hipMemcpyAsync(prefix_dev, prefix, slots * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
+  PHMRF_HIP(hipMemsetAsync(hist_dev, 0, nbins * sizeof(unsigned long long), b->stream));
   if (last > first) {
     const dim3 grid(grid_of(last - first, 256, HIST_GRID_CAP), S * J);
     const size_t lds = (size_t)K * 256 * sizeof(unsigned);
-    hipLaunchKernelGGL(state_hist_kernel, grid, dim3(256), lds, b->stream, b->X, b->labels, first, last, S, K, J, shift, w.prefix,
-                       w.hist);
+    hipLaunchKernelGGL(state_hist_kernel, grid, dim3(256), lds, b->stream, b->X, b->labels, first, last, S, K, J, shift, prefix_dev,
+                       hist_dev);
     PHMRF_HIP(hipGetLastError());
   }
   static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the bins are read back as they are");
-  PHMRF_HIP(hipMemcpyAsync(hist, w.hist, nbins * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
+  PHMRF_HIP(hipMemcpyAsync(hist, hist_dev, nbins * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
   PHMRF_HIP(hipStreamSynchronize(b->stream));
   return PHMRF_OK;
 }
@@ -229,29 +217,29 @@ int phmrf_state_moments(phmrf_block_t b, int64_t dist0, int64_t* count, double* 
   PHMRF_TRY(owned_range(b, &first, &last));
   if (bands_or_null) {
     PHMRF_CHECK(b->has_grid, PHMRF_ERR_STATE, "distance bands need the grid geometry (phmrf_block_set_grid / build_grid_graph)");
-    const int64_t reach = (dist0 < 0 ? -dist0 : dist0) + (b->H > b->W ? b->H : b->W);
-    PHMRF_CHECK(dist0 > -((int64_t)1 << 31) && reach < ((int64_t)1 << 31), PHMRF_ERR_INVALID,
-                "a distance |dist0 + j - i| of 2^31 or more has no band");
+    PHMRF_TRY(check_reach(dist0, b->H, b->W));
   }
   const int K = b->K, S = b->S, M = K * 2 * S, NC = K * (1 + PHMRF_DIFF_BANDS);
   const int rows = grid_of(last - first, 64, std::min(MOM_GRID_CAP, MOM_PARTIAL_CAP / M));
-  ProfileWork w;
-  PHMRF_TRY(alloc(&w.partial, (size_t)rows * M));
-  PHMRF_TRY(alloc(&w.sums, (size_t)M));
-  PHMRF_TRY(alloc(&w.counts, (size_t)NC));
-  PHMRF_HIP(hipMemsetAsync(w.counts, 0, (size_t)NC * sizeof(unsigned long long), b->stream));
-  PHMRF_HIP(hipMemsetAsync(w.sums, 0, (size_t)M * sizeof(double), b->stream));
+  Buffers buf;
+  double *partial, *sums_dev;
+  unsigned long long* counts;                // [K] counts, then [K * 32] bands
+  PHMRF_TRY(buf.get(&partial, (size_t)rows * M));
+  PHMRF_TRY(buf.get(&sums_dev, (size_t)M));
+  PHMRF_TRY(buf.get(&counts, (size_t)NC));
+  PHMRF_HIP(hipMemsetAsync(counts, 0, (size_t)NC * sizeof(unsigned long long), b->stream));
+  PHMRF_HIP(hipMemsetAsync(sums_dev, 0, (size_t)M * sizeof(double), b->stream));
   if (last > first) {
     const size_t lds = (size_t)M * sizeof(double) + (size_t)NC * sizeof(unsigned);
     hipLaunchKernelGGL(state_moments_kernel, dim3(rows), dim3(64), lds, b->stream, b->X, b->labels, first, last, S, K, b->W,
-                       b->diagonal, (long long)dist0, w.partial, w.counts, bands_or_null ? w.counts + K : nullptr);
-    hipLaunchKernelGGL(state_moments_reduce_kernel, dim3(M), dim3(256), 0, b->stream, w.partial, rows, M, w.sums);
+                       b->diagonal, (long long)dist0, partial, counts, bands_or_null ? counts + K : nullptr);
+    hipLaunchKernelGGL(state_moments_reduce_kernel, dim3(M), dim3(256), 0, b->stream, partial, rows, M, sums_dev);
     PHMRF_HIP(hipGetLastError());
   }
   std::vector<unsigned long long> got((size_t)NC);
   std::vector<double> sums((size_t)M);
-  PHMRF_HIP(hipMemcpyAsync(got.data(), w.counts, (size_t)NC * sizeof(unsigned long long), hipMemcpyDeviceToHost, b->stream));
-  PHMRF_HIP(hipMemcpyAsync(sums.data(), w.sums, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+  PHMRF_HIP(hipMemcpyAsync(got.data(), counts, (size_t)NC * sizeof(unsigned long long), hipMemcpyDeviceToHost, b->stream));
+  PHMRF_HIP(hipMemcpyAsync(sums.data(), sums_dev, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, b->stream));
   PHMRF_HIP(hipStreamSynchronize(b->stream));
   for (int k = 0; k < K; ++k) count[k] = (int64_t)got[k];
   for (int t = 0; t < K * S; ++t) {

@@ -204,19 +204,6 @@ __global__ __launch_bounds__(256) void render_colour_kernel(const uint8_t* __res
   }
 }
 
-// device buffers of one call, released on every way out
-struct RenderWork {
-  uint8_t* planes = nullptr;
-  uint8_t* rgb = nullptr;
-  uint8_t* colours = nullptr;
-  int* bad = nullptr;
-  ~RenderWork() {
-    void* all[] = {planes, rgb, colours, bad};
-    for (void* p : all)
-      if (p) (void)hipFree(p);
-  }
-};
-
 }  // namespace
 }  // namespace phmrf
 
@@ -228,9 +215,7 @@ int phmrf_render_states(const uint8_t* labels_dev, const float* conf_dev_or_null
                         int diagonal, int K, int factor, const uint8_t* palette_host, const uint8_t* extra_host, int outline,
                         uint8_t* planes_host_or_null, uint8_t* rgb_host_or_null, void* hip_stream) {
   PHMRF_CHECK(labels_dev && palette_host && extra_host, PHMRF_ERR_INVALID, "NULL labels, palette or extra colours");
-  PHMRF_CHECK(H >= 1 && W >= 1, PHMRF_ERR_INVALID, "H and W must be >= 1");
-  PHMRF_CHECK(diagonal == 0 || diagonal == 1, PHMRF_ERR_INVALID, "diagonal must be 0 or 1");
-  PHMRF_CHECK(!diagonal || H == W, PHMRF_ERR_INVALID, "a diagonal block is square (H == W)");
+  PHMRF_TRY(check_region(H, W, diagonal));
   PHMRF_CHECK(K >= 1 && K <= 64, PHMRF_ERR_INVALID, "K must be in 1 .. 64");
   PHMRF_CHECK(factor >= 1, PHMRF_ERR_INVALID, "factor must be >= 1");
   PHMRF_CHECK(factor <= RENDER_MAX_FACTOR, PHMRF_ERR_UNSUPPORTED, "factor must be <= 32768");
@@ -241,15 +226,17 @@ int phmrf_render_states(const uint8_t* labels_dev, const float* conf_dev_or_null
   const int per_row = (int)((w + RENDER_TILE - 1) / RENDER_TILE);
   const int64_t ntiles = diagonal ? (int64_t)RENDER_TILE * grid_row_first<int64_t>(per_row, per_row, 1) : h * per_row;
 
-  RenderWork work;
-  PHMRF_TRY(alloc(&work.planes, 3 * plane));
-  PHMRF_TRY(alloc(&work.bad, 1));
-  PHMRF_HIP(hipMemsetAsync(work.bad, 0, sizeof(int), st));
+  Buffers buf;
+  uint8_t* planes;
+  int* flag;
+  PHMRF_TRY(buf.get(&planes, 3 * plane));
+  PHMRF_TRY(buf.get(&flag, 1));
+  PHMRF_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
   hipLaunchKernelGGL(render_vote_kernel, dim3(grid_of(ntiles, 1, RENDER_GRID_CAP)), dim3(256), 0, st, labels_dev, conf_dev_or_null,
-                     mark_dev_or_null, H, W, diagonal, K, factor, (int)h, (int)w, per_row, ntiles, work.planes, work.bad);
+                     mark_dev_or_null, H, W, diagonal, K, factor, (int)h, (int)w, per_row, ntiles, planes, flag);
   PHMRF_HIP(hipGetLastError());
   int bad = 0;
-  PHMRF_HIP(hipMemcpyAsync(&bad, work.bad, sizeof(int), hipMemcpyDeviceToHost, st));
+  PHMRF_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
   PHMRF_HIP(hipStreamSynchronize(st));
   PHMRF_CHECK(!(bad & 1), PHMRF_ERR_INVALID, "a label is >= K");
   PHMRF_CHECK(!(bad & 2), PHMRF_ERR_INVALID, "a confidence is not a finite number in [0, 1]");
@@ -257,16 +244,17 @@ int phmrf_render_states(const uint8_t* labels_dev, const float* conf_dev_or_null
     std::vector<uint8_t> colours((size_t)3 * K + 6);
     for (int t = 0; t < 3 * K; ++t) colours[(size_t)t] = palette_host[t];
     for (int t = 0; t < 6; ++t) colours[(size_t)3 * K + t] = extra_host[t];
-    PHMRF_TRY(alloc(&work.rgb, 3 * plane));
-    PHMRF_TRY(alloc(&work.colours, colours.size()));
-    PHMRF_HIP(hipMemcpyAsync(work.colours, colours.data(), colours.size(), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(render_colour_kernel, dim3(grid_of((int64_t)plane, 256, RENDER_GRID_CAP)), dim3(256), 0, st, work.planes,
-                       (int)h, (int)w, K, outline ? 1 : 0, work.colours, work.rgb);
+    uint8_t *rgb, *colours_dev;
+    PHMRF_TRY(buf.get(&rgb, 3 * plane));
+    PHMRF_TRY(buf.get(&colours_dev, colours.size()));
+    PHMRF_HIP(hipMemcpyAsync(colours_dev, colours.data(), colours.size(), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(render_colour_kernel, dim3(grid_of((int64_t)plane, 256, RENDER_GRID_CAP)), dim3(256), 0, st, planes,
+                       (int)h, (int)w, K, outline ? 1 : 0, colours_dev, rgb);
     PHMRF_HIP(hipGetLastError());
-    PHMRF_HIP(hipMemcpyAsync(rgb_host_or_null, work.rgb, 3 * plane, hipMemcpyDeviceToHost, st));
+    PHMRF_HIP(hipMemcpyAsync(rgb_host_or_null, rgb, 3 * plane, hipMemcpyDeviceToHost, st));
   }
   if (planes_host_or_null)
-    PHMRF_HIP(hipMemcpyAsync(planes_host_or_null, work.planes, 3 * plane, hipMemcpyDeviceToHost, st));
+    PHMRF_HIP(hipMemcpyAsync(planes_host_or_null, planes, 3 * plane, hipMemcpyDeviceToHost, st));
   PHMRF_HIP(hipStreamSynchronize(st));
   return PHMRF_OK;
 }

@@ -1,7 +1,8 @@
 // What the post-processing's kernel files share (smooth.hip, compare.hip, profile.hip, domains.hip, tracks.hip, enrich.hip):
 // the capped grid, the wave helpers of their integer accumulations -- one atomic per RUN of equal destination among
-// consecutive lanes, because state maps are piecewise constant --, the split of a label row into aligned words (tracks.hip,
-// enrich.hip) and the full-matrix area of a grid component.
+// consecutive lanes, because state maps are piecewise constant --, the split of a label row into aligned words and the tiles of
+// a distance window (tracks.hip, enrich.hip), the full-matrix area of a grid component, and on the host the owner of a
+// call's device buffers and the checks of a region's arguments (preprocess.hip and render.hip take those too).
 #pragma once
 
 #include "common.h"
@@ -82,9 +83,112 @@ __device__ __forceinline__ long long component_area(int64_t v, int diagonal, con
 __host__ __device__ __forceinline__ bool unit_bits(uint32_t u) { return u <= 0x3f800000u || u == 0x80000000u; }
 __device__ __forceinline__ bool unit_conf(float c) { return unit_bits(__float_as_uint(c)); }
 
-template <typename T>
-int alloc(T** p, size_t count) {
-  PHMRF_HIP(hipMalloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(T)));
+// rows [i0, i1) and columns [j0, j1) of the storage; whole: every cell is inside the distance window; the cells' distances
+// lie in [near, near + nd)
+struct WindowTile {
+  int i0, i1, j0, j1, near, nd;
+  bool whole;
+};
+
+// Tile T of a region cut into tiles of TILE_H storage rows by TILE_W storage columns, per_row of them side by side (a
+// diagonal block: the upper triangle of the per_row x per_row grid of TILE_W-square super-tiles, TILE_W / TILE_H tiles each);
+// false for a tile of the last super-tile row's padding, and for a tile wholly outside the window d_lo <= |dist0 + j - i|
+// <= d_hi (the same answer for the whole workgroup)
+template <int TILE_H, int TILE_W>
+__device__ __forceinline__ bool window_tile(int64_t T, int H, int W, int diagonal, int per_row, int dist0, int d_lo, int d_hi,
+                                            WindowTile* t) {
+  constexpr int PER_SUPER = TILE_W / TILE_H;
+  int ti, tj;
+  if (diagonal) {
+    int g;
+    grid_coords(T / PER_SUPER, per_row, 1, &g, &tj);
+    ti = g * PER_SUPER + (int)(T % PER_SUPER);
+  } else {
+    grid_coords(T, per_row, 0, &ti, &tj);
+  }
+  const int64_t i0 = (int64_t)ti * TILE_H;
+  if (i0 >= H) return false;
+  int64_t j0 = (int64_t)tj * TILE_W;
+  const int64_t i1 = i0 + TILE_H < H ? i0 + TILE_H : H;
+  const int64_t j1 = j0 + TILE_W < W ? j0 + TILE_W : W;
+  t->i0 = (int)i0;
+  t->i1 = (int)i1;
+  t->j0 = (int)j0;
+  t->j1 = (int)j1;
+  if (diagonal && j0 < i0) j0 = i0;                    // the stored cells of the tile start at the diagonal
+  if (j0 >= j1) return false;
+  // the range of dist0 + j - i over the tile (|dist0| + H + W < 2^31: an int holds every distance)
+  const int x_lo = dist0 + (int)j0 - ((int)i1 - 1), x_hi = dist0 + ((int)j1 - 1) - (int)i0;
+  const int a_lo = x_lo < 0 ? -x_lo : x_lo, a_hi = x_hi < 0 ? -x_hi : x_hi;
+  const int far = a_lo > a_hi ? a_lo : a_hi;
+  const int near = (x_lo <= 0 && x_hi >= 0) ? 0 : (a_lo < a_hi ? a_lo : a_hi);
+  if (far < d_lo || near > d_hi) return false;
+  t->whole = near >= d_lo && far <= d_hi;
+  t->near = near;
+  t->nd = far - near + 1;                              // <= x_hi - x_lo + 1 <= TILE_H + TILE_W - 1
+  return true;
+}
+
+// ---- what the entry points share on the host ---------------------------------------------------------------------------
+
+// The device allocations of one call, freed on every way out.
+class Buffers {
+ public:
+  Buffers() = default;
+  Buffers(const Buffers&) = delete;
+  Buffers& operator=(const Buffers&) = delete;
+  ~Buffers() {
+    for (void* p : owned_) (void)hipFree(p);
+  }
+  template <typename T>
+  int get(T** p, size_t count) {                       // *p = max(count, 1) elements
+    PHMRF_HIP(hipMalloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(T)));
+    owned_.push_back(*p);
+    return PHMRF_OK;
+  }
+  template <typename T>
+  int release(T** p) {                                 // frees *p (null: nothing to do) ahead of time, to get it again larger
+    for (size_t t = 0; t < owned_.size(); ++t)
+      if (*p && owned_[t] == *p) {
+        owned_.erase(owned_.begin() + t);
+        PHMRF_HIP(hipFree(*p));
+        break;
+      }
+    *p = nullptr;
+    return PHMRF_OK;
+  }
+
+ private:
+  std::vector<void*> owned_;
+};
+
+// H, W >= 1, diagonal in {0, 1}, a diagonal block square; *n = the region's stored nodes
+inline int check_region(int H, int W, int diagonal, int64_t* n = nullptr) {
+  PHMRF_CHECK(H >= 1 && W >= 1, PHMRF_ERR_INVALID, "H and W must be >= 1");
+  PHMRF_CHECK(diagonal == 0 || diagonal == 1, PHMRF_ERR_INVALID, "diagonal must be 0 or 1");
+  PHMRF_CHECK(!diagonal || H == W, PHMRF_ERR_INVALID, "a diagonal block is square (H == W)");
+  if (n) *n = grid_row_first<int64_t>(H, W, diagonal);
+  return PHMRF_OK;
+}
+
+// the states of one map (KB: a second map's, `names` then says "KA and KB")
+inline int check_states(int K, int KB = 1, const char* names = "K") {
+  PHMRF_CHECK(K >= 1 && KB >= 1, PHMRF_ERR_INVALID, std::string(names) + " must be >= 1");
+  PHMRF_CHECK(K <= 64 && KB <= 64, PHMRF_ERR_UNSUPPORTED, std::string(names) + " must be <= 64");
+  return PHMRF_OK;
+}
+
+// node ids and the 64 past the last that a wave may form fit an int
+inline int check_nodes(int64_t n, const char* msg = "the region must have fewer than 2^31 - 64 nodes") {
+  PHMRF_CHECK(n < ((int64_t)1 << 31) - 64, PHMRF_ERR_UNSUPPORTED, msg);
+  return PHMRF_OK;
+}
+
+// every distance |dist0 + j - i| of an H x W region is below 2^31 (band_of, the int distances of domains.hip)
+inline int check_reach(int64_t dist0, int H, int W, const char* suffix = " has no band") {
+  const int64_t reach = (dist0 < 0 ? -dist0 : dist0) + (H > W ? H : W);
+  PHMRF_CHECK(dist0 > -((int64_t)1 << 31) && reach < ((int64_t)1 << 31), PHMRF_ERR_INVALID,
+              std::string("a distance |dist0 + j - i| of 2^31 or more") + suffix);
   return PHMRF_OK;
 }
 

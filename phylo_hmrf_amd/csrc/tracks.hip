@@ -34,45 +34,6 @@ constexpr int TRACKS_STRIDE = 65;        // u32 words per tile row / column: 64 
 constexpr int TRACKS_ROWS_PER_WAVE = TRACKS_TILE_H / 4;          // a workgroup is four waves
 constexpr int TRACKS_PER_SUPER = TRACKS_TILE_W / TRACKS_TILE_H;   // tiles of a square super-tile (diagonal blocks)
 
-// rows [i0, i1) and columns [j0, j1) of the storage; whole: every cell is inside the window
-struct TracksTile {
-  int i0, i1, j0, j1;
-  bool whole;
-};
-
-// tile T of the region; false for a tile of the last super-tile row's padding, and for a tile wholly outside the window
-// (the same answer for the whole workgroup)
-__device__ __forceinline__ bool tracks_tile(int64_t T, int H, int W, int diagonal, int per_row, int dist0, int d_lo, int d_hi,
-                                            TracksTile* t) {
-  int ti, tj;
-  if (diagonal) {                                      // the upper triangle of the per_row x per_row grid of super-tiles
-    int g;
-    grid_coords(T / TRACKS_PER_SUPER, per_row, 1, &g, &tj);
-    ti = g * TRACKS_PER_SUPER + (int)(T % TRACKS_PER_SUPER);
-  } else {
-    grid_coords(T, per_row, 0, &ti, &tj);
-  }
-  const int64_t i0 = (int64_t)ti * TRACKS_TILE_H;
-  if (i0 >= H) return false;
-  int64_t j0 = (int64_t)tj * TRACKS_TILE_W;
-  const int64_t i1 = i0 + TRACKS_TILE_H < H ? i0 + TRACKS_TILE_H : H;
-  const int64_t j1 = j0 + TRACKS_TILE_W < W ? j0 + TRACKS_TILE_W : W;
-  t->i0 = (int)i0;
-  t->i1 = (int)i1;
-  t->j0 = (int)j0;
-  t->j1 = (int)j1;
-  if (diagonal && j0 < i0) j0 = i0;                    // the stored cells of the tile start at the diagonal
-  if (j0 >= j1) return false;
-  // the range of dist0 + j - i over the tile (|dist0| + H + W < 2^31: an int holds every distance)
-  const int x_lo = dist0 + (int)j0 - ((int)i1 - 1), x_hi = dist0 + ((int)j1 - 1) - (int)i0;
-  const int a_lo = x_lo < 0 ? -x_lo : x_lo, a_hi = x_hi < 0 ? -x_hi : x_hi;
-  const int far = a_lo > a_hi ? a_lo : a_hi;
-  const int near = (x_lo <= 0 && x_hi >= 0) ? 0 : (a_lo < a_hi ? a_lo : a_hi);
-  if (far < d_lo || near > d_hi) return false;
-  t->whole = near >= d_lo && far <= d_hi;
-  return true;
-}
-
 // table: u32 [(H + W) K], the rows' counts and then the columns' (a diagonal block: [H K]); d_hi: INT_MAX for no upper limit
 __global__ __launch_bounds__(256) void tracks_kernel(const uint8_t* __restrict__ labels, int H, int W, int diagonal, int dist0,
                                                      int K, int d_lo, int d_hi, int per_row, int64_t ntiles,
@@ -87,8 +48,8 @@ __global__ __launch_bounds__(256) void tracks_kernel(const uint8_t* __restrict__
   unsigned* const col_out = table + (diagonal ? (size_t)0 : (size_t)H * K);
   bool wrong = false;
   for (int64_t T = blockIdx.x; T < ntiles; T += gridDim.x) {
-    TracksTile t;
-    if (!tracks_tile(T, H, W, diagonal, per_row, dist0, d_lo, d_hi, &t)) continue;
+    WindowTile t;
+    if (!window_tile<TRACKS_TILE_H, TRACKS_TILE_W>(T, H, W, diagonal, per_row, dist0, d_lo, d_hi, &t)) continue;
     // the wave's rows i0 + wave, i0 + wave + 4, ...: every load of the tile is issued before the first count
     uint32_t word[TRACKS_ROWS_PER_WAVE];
     int single[TRACKS_ROWS_PER_WAVE];
@@ -173,17 +134,6 @@ __global__ __launch_bounds__(256) void tracks_kernel(const uint8_t* __restrict__
   if (wrong) atomicOr(bad, 1);
 }
 
-// device buffers of one call, released on every way out
-struct TracksWork {
-  unsigned* table = nullptr;
-  int* bad = nullptr;
-  ~TracksWork() {
-    void* all[] = {table, bad};
-    for (void* p : all)
-      if (p) (void)hipFree(p);
-  }
-};
-
 }  // namespace
 }  // namespace phmrf
 
@@ -204,7 +154,7 @@ int phmrf_state_tracks(const uint8_t* labels_dev, int H, int W, int diagonal, in
   PHMRF_CHECK(d_max == -1 || d_max >= d_min, PHMRF_ERR_INVALID, "d_max must be >= d_min, or -1 for no upper limit");
   PHMRF_CHECK(K <= 64, PHMRF_ERR_UNSUPPORTED, "K must be <= 64");
   const int64_t n = grid_row_first<int64_t>(H, W, diagonal);
-  PHMRF_CHECK(n < ((int64_t)1 << 31) - 64, PHMRF_ERR_UNSUPPORTED, "n must be below 2^31 - 64");
+  PHMRF_TRY(check_nodes(n, "n must be below 2^31 - 64"));
   PHMRF_CHECK(dist0 > -((int64_t)1 << 31) && dist0 < ((int64_t)1 << 31) &&
                   (dist0 < 0 ? -dist0 : dist0) + H + W < ((int64_t)1 << 31),
               PHMRF_ERR_UNSUPPORTED, "|dist0| + H + W must be below 2^31");
@@ -214,22 +164,24 @@ int phmrf_state_tracks(const uint8_t* labels_dev, int H, int W, int diagonal, in
   const int64_t ntiles = diagonal ? (int64_t)TRACKS_PER_SUPER * grid_row_first<int64_t>(per_row, per_row, 1)
                                   : (int64_t)((H + TRACKS_TILE_H - 1) / TRACKS_TILE_H) * per_row;
 
-  TracksWork work;
-  PHMRF_TRY(alloc(&work.table, words));
-  PHMRF_TRY(alloc(&work.bad, 1));
-  PHMRF_HIP(hipMemsetAsync(work.table, 0, words * sizeof(unsigned), st));
-  PHMRF_HIP(hipMemsetAsync(work.bad, 0, sizeof(int), st));
+  Buffers buf;
+  unsigned* table;
+  int* flag;
+  PHMRF_TRY(buf.get(&table, words));
+  PHMRF_TRY(buf.get(&flag, 1));
+  PHMRF_HIP(hipMemsetAsync(table, 0, words * sizeof(unsigned), st));
+  PHMRF_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
   // every distance is below INT_MAX: a d_min up there leaves nothing inside, a d_max up there is no limit
   const int d_lo = d_min < INT_MAX ? (int)d_min : INT_MAX, d_hi = (d_max == -1 || d_max > INT_MAX) ? INT_MAX : (int)d_max;
   hipLaunchKernelGGL(tracks_kernel, dim3(grid_of(ntiles, 1, TRACKS_GRID_CAP)), dim3(256), 0, st, labels_dev, H, W, diagonal,
-                     (int)dist0, K, d_lo, d_hi, per_row, ntiles, work.table, work.bad);
+                     (int)dist0, K, d_lo, d_hi, per_row, ntiles, table, flag);
   PHMRF_HIP(hipGetLastError());
   int bad = 0;
-  PHMRF_HIP(hipMemcpyAsync(&bad, work.bad, sizeof(int), hipMemcpyDeviceToHost, st));
+  PHMRF_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
   PHMRF_HIP(hipStreamSynchronize(st));
   PHMRF_CHECK(!bad, PHMRF_ERR_INVALID, "a label inside the window is >= K");
   std::vector<unsigned> got(words);
-  PHMRF_HIP(hipMemcpyAsync(got.data(), work.table, words * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  PHMRF_HIP(hipMemcpyAsync(got.data(), table, words * sizeof(unsigned), hipMemcpyDeviceToHost, st));
   PHMRF_HIP(hipStreamSynchronize(st));
   const size_t nrow = (size_t)H * (size_t)K;
   for (size_t t = 0; t < nrow; ++t) rows_host[t] = (int64_t)got[t];

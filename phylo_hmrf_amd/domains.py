@@ -16,8 +16,9 @@ import os
 
 import numpy as np
 
-from .compare import CONF_ONE, FIRST_CAPACITY, _conf, _count, _device, _stem
-from .smooth import check_len_vec, check_state_vec, default_max_area
+from .compare import count_pairs
+from .maps import (CONF_ONE, FIRST_CAPACITY, check_len_vec, check_state_vec, conf_array, default_max_area, device, list_rows,
+                   load_map, regions, stem)
 
 STATE_DOMAIN_COLS = 16           # include/phmrf.h PHMRF_STATE_DOMAIN_COLS
 GRID_CAP = 1024                  # csrc/domains.hip DOM_GRID_CAP: workgroups (of 256 lanes) of its kernels
@@ -43,9 +44,9 @@ def state_domains(state_vec, len_vec, conf=None, min_area=None):
     if min_area is not None and int(min_area) < 1:
         raise ValueError("min_area must be >= 1 (None: the smoothing's area rule + 1)")
     n, R = s.shape[0], L.shape[0]
-    conf = None if conf is None else _conf(conf, n, "conf")
+    conf = None if conf is None else conf_array(conf, n, "conf")
     K = int(s.max()) + 1 if n else 1
-    lib, dev, stream = _device()
+    lib, dev, stream = device()
     s_t = torch.from_numpy(s.astype(np.uint8)).to(dev)
     c_t = None if conf is None else torch.from_numpy(conf).to(dev)
     out_t = torch.full((n,), -1, dtype=torch.int32, device=dev)
@@ -54,30 +55,24 @@ def state_domains(state_vec, len_vec, conf=None, min_area=None):
     nodes = np.zeros(K, dtype=np.int64)
     rows, offset = [], 0
     null = ctypes.c_void_p(None)
-    for r, row in enumerate(L):
-        lo, hi, H, W, diag = int(row[1]), int(row[2]), int(row[3]), int(row[4]), int(row[8])
+    for r, lo, hi, H, W, diag, dist0 in regions(L):
         area = default_max_area(H) + 1 if min_area is None else int(min_area)
         labels = ctypes.c_void_p(s_t[lo:hi].data_ptr())
         _lib.check(lib.phmrf_state_adjacency(labels, H, W, diag, K, _lib.ptr_i64(adjacency[r]), stream))
-        nodes += np.diagonal(_count(lib, stream, s_t[lo:hi], s_t[lo:hi], K, K))
+        nodes += np.diagonal(count_pairs(lib, stream, s_t[lo:hi], s_t[lo:hi], K, K))
 
-        def call(capacity):
-            table = np.zeros((max(capacity, 1), STATE_DOMAIN_COLS), dtype=np.int64)
-            found = ctypes.c_int64(0)
+        def call(capacity, table, found):
             _lib.check(lib.phmrf_state_domains(
-                labels, null if c_t is None else ctypes.c_void_p(c_t[lo:hi].data_ptr()), H, W, diag, int(row[6]) - int(row[5]),
+                labels, null if c_t is None else ctypes.c_void_p(c_t[lo:hi].data_ptr()), H, W, diag, dist0,
                 K, area, ctypes.c_void_p(out_t[lo:hi].data_ptr()), capacity, _lib.ptr_i64(table), ctypes.byref(found),
                 _lib.ptr_i64(components[r]), stream))
-            return table, int(found.value)
 
-        table, found = call(FIRST_CAPACITY)
-        if found > FIRST_CAPACITY:
-            table, found = call(found)
+        table = list_rows(call, STATE_DOMAIN_COLS, FIRST_CAPACITY)
         if offset:
             view = out_t[lo:hi]
             view[view >= 0] += offset
-        offset += found
-        rows.append(np.concatenate([np.full((found, 1), r, dtype=np.int64), table[:found]], axis=1))
+        offset += table.shape[0]
+        rows.append(np.concatenate([np.full((table.shape[0], 1), r, dtype=np.int64), table], axis=1))
     domains = np.concatenate(rows) if rows else np.zeros((0, STATE_DOMAIN_COLS + 1), dtype=np.int64)
     if conf is None:
         domain_conf = np.full(domains.shape[0], np.nan)
@@ -117,16 +112,6 @@ def domain_lines(domains, domain_conf, len_vec, resolution):
     return lines
 
 
-def load_map(path, field="state_vec"):
-    """-> (states, len_vec, conf or None) of an estimate_ou_*.mat / segment_*.mat / smooth_*.mat.  Host only."""
-    import scipy.io
-    d = scipy.io.loadmat(path)
-    if field not in d or "len_vec" not in d:
-        raise ValueError("%s holds no %s / len_vec" % (path, field))
-    s = check_state_vec(d[field])
-    return s, check_len_vec(d["len_vec"], s.shape[0]), (np.asarray(d["conf"]).reshape(-1) if "conf" in d else None)
-
-
 def domains_files(path, output_path, resolution, field="state_vec", min_area=None):
     """The command line's --domains: list the domains of the `field` of one .mat, write domains_<stem>.mat and
     domains_<stem>.txt under output_path.  -> the .mat"""
@@ -137,8 +122,8 @@ def domains_files(path, output_path, resolution, field="state_vec", min_area=Non
     res = state_domains(s, L, conf, min_area=min_area)
     os.makedirs(output_path, exist_ok=True)
     areas = np.array([default_max_area(r[3]) + 1 if min_area is None else int(min_area) for r in L], dtype=np.int64)
-    out = os.path.join(output_path, "domains_%s.mat" % _stem(path))
+    out = os.path.join(output_path, "domains_%s.mat" % stem(path))
     scipy.io.savemat(out, dict(res, len_vec=L, domains_field=field, domains_area=areas, resolution=int(resolution)))
-    with open(os.path.join(output_path, "domains_%s.txt" % _stem(path)), "wb") as fh:
+    with open(os.path.join(output_path, "domains_%s.txt" % stem(path)), "wb") as fh:
         fh.write("".join(domain_lines(res["domains"], res["domain_conf"], L, resolution)).encode())
     return out

@@ -24,8 +24,7 @@ import os
 
 import numpy as np
 
-from .compare import _device, _stem
-from .smooth import MAX_STATES, check_len_vec, check_state_vec
+from .maps import MAX_STATES, check_len_vec, check_state_vec, device, load_map, stem
 from .tracks import check_windows, covered_bins, parse_windows
 
 GRID_CAP = 1024                  # csrc/enrich.hip ENRICH_GRID_CAP: workgroups (of 256 lanes) of its kernels
@@ -189,7 +188,7 @@ def pair_enrichment(state_vec, len_vec, bin_class, bin_seg=None, window=(0, -1),
     C = max([1] + [int(v.max()) + 1 for v in classes.values() if v.size]) if C is None else int(C)
     if C < 1 or C > MAX_CLASSES:
         raise ValueError("C must be in 1 .. %d (class 0 and at most %d names)" % (MAX_CLASSES, MAX_CLASSES - 1))
-    lib, dev, stream = _device()
+    lib, dev, stream = device()
     P = 2 * C * C
     ranges = [distance_range(r[3], r[4], int(r[8]), int(r[6]) - int(r[5]), d_min, d_max) for r in L]
     held = [g for g in ranges if g is not None]
@@ -255,7 +254,6 @@ def enrich_files(path, bed, output_path, resolution, field="state_vec", window_b
     annotation file `bed`.  Writes under output_path enrich_<stem>.npz (pair_enrichment's arrays, names, skipped_lines,
     class_<chrom> and seg_<chrom>, len_vec, resolution, enrich_field, window_bp, segments; no pickles) and enrich_<stem>.txt
     (enrich_lines).  -> the .npz"""
-    from .domains import load_map
     res = int(resolution)
     if res < 1:
         raise ValueError("resolution must be >= 1")
@@ -266,14 +264,14 @@ def enrich_files(path, bed, output_path, resolution, field="state_vec", window_b
     ann = read_annotation(bed, L, res, segments=bool(segments))
     result = pair_enrichment(s, L, ann["bin_class"], ann["bin_seg"], window=wins[0], C=len(ann["names"]))
     os.makedirs(output_path, exist_ok=True)
-    stem = _stem(path)
-    out = os.path.join(output_path, "enrich_%s.npz" % stem)
+    name = stem(path)
+    out = os.path.join(output_path, "enrich_%s.npz" % name)
     extra = {"class_%d" % c: v for c, v in ann["bin_class"].items()}
     if ann["bin_seg"] is not None:
         extra.update({"seg_%d" % c: v for c, v in ann["bin_seg"].items()})
     np.savez(out, len_vec=L, resolution=np.int64(res), enrich_field=np.array(field), window_bp=np.array(str(window_bp)),
              segments=np.int64(bool(segments)), names=np.array(ann["names"]), skipped_lines=np.int64(ann["skipped_lines"]),
              **extra, **result)
-    with open(os.path.join(output_path, "enrich_%s.txt" % stem), "wb") as fh:
+    with open(os.path.join(output_path, "enrich_%s.txt" % name), "wb") as fh:
         fh.write("".join(enrich_lines(result, ann["names"])).encode())
     return out

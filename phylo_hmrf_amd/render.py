@@ -16,8 +16,7 @@ import zlib
 
 import numpy as np
 
-from .compare import _conf, _device, _stem
-from .smooth import MAX_STATES, check_len_vec, check_state_vec
+from .maps import MAX_STATES, check_len_vec, check_state_vec, conf_array, device, load_map, regions, stem
 
 GRID_CAP = 1024                  # csrc/render.hip RENDER_GRID_CAP: workgroups (of 256 lanes) of its kernels
 TILE = 32                        # csrc/render.hip RENDER_TILE: consecutive pixels of one pixel row a workgroup votes at a time
@@ -108,19 +107,18 @@ def render_states(state_vec, len_vec, conf=None, mark=None, max_side=2048, facto
     K = int(s.max()) + 1 if n else 1
     pal = _palette(palette, K)
     extra = np.concatenate([_colour(highlight, "highlight"), _colour(outline_colour, "outline_colour")])
-    conf = None if conf is None else _conf(conf, n, "conf")
+    conf = None if conf is None else conf_array(conf, n, "conf")
     if mark is not None:
         mark = np.ascontiguousarray(np.asarray(mark).reshape(-1) != 0).astype(np.uint8)
         if mark.shape[0] != n:
             raise ValueError("mark has %d entries for %d nodes" % (mark.shape[0], n))
-    lib, dev, stream = _device()
+    lib, dev, stream = device()
     s_t = torch.from_numpy(s.astype(np.uint8)).to(dev)
     c_t = None if conf is None else torch.from_numpy(conf).to(dev)
     m_t = None if mark is None else torch.from_numpy(mark).to(dev)
     null = ctypes.c_void_p(None)
     out = []
-    for row in L:
-        lo, hi, H, W, diag = int(row[1]), int(row[2]), int(row[3]), int(row[4]), int(row[8])
+    for _, lo, hi, H, W, diag, _ in regions(L):
         f = choose_factor(H, W, max_side) if factor is None else int(factor)
         h, w = -(-H // f), -(-W // f)
         planes = np.zeros((3, h, w), dtype=np.uint8)
@@ -170,7 +168,6 @@ def render_files(path, output_path, field="state_vec", max_side=2048, palette_pa
     output_path one render_<stem>_r<region>_chr<chrom>.png per region (region: the row of len_vec), render_<stem>.npz (the
     planes state_<r>, conf8_<r>, mark8_<r>, and factor, palette, len_vec and the settings; no pickles) and
     render_<stem>_legend.txt (per state: state + 1, R, G, B).  -> the .npz"""
-    from .domains import load_map
     if int(max_side) < 1:
         raise ValueError("max_side must be >= 1")
     s, L, conf = load_map(path, field)
@@ -182,18 +179,18 @@ def render_files(path, output_path, field="state_vec", max_side=2048, palette_pa
     res = render_states(s, L, conf=conf if use_conf else None, mark=mark, max_side=int(max_side), palette=palette,
                         outline=bool(outline))
     os.makedirs(output_path, exist_ok=True)
-    stem = _stem(path)
+    base = stem(path)
     arrays = dict(factor=np.array([r["factor"] for r in res], dtype=np.int64), palette=palette, len_vec=L,
                   render_field=np.array(field), render_side=np.int64(max_side), render_outline=np.int64(bool(outline)),
                   render_conf=np.int64(bool(use_conf)), render_mark=np.array(os.path.basename(mark_path)),
                   highlight=np.array(HIGHLIGHT, dtype=np.uint8), outline_colour=np.array(OUTLINE, dtype=np.uint8))
     for r, (row, img) in enumerate(zip(L, res)):
-        write_png(os.path.join(output_path, "render_%s_r%d_chr%d.png" % (stem, r, int(row[9]))), img["rgb"])
+        write_png(os.path.join(output_path, "render_%s_r%d_chr%d.png" % (base, r, int(row[9]))), img["rgb"])
         for name in ("state", "conf8", "mark8"):
             arrays["%s_%d" % (name, r)] = img[name]
-    out = os.path.join(output_path, "render_%s.npz" % stem)
+    out = os.path.join(output_path, "render_%s.npz" % base)
     np.savez(out, **arrays)
-    with open(os.path.join(output_path, "render_%s_legend.txt" % stem), "w") as fh:
+    with open(os.path.join(output_path, "render_%s_legend.txt" % base), "w") as fh:
         for k in range(K):
             fh.write("%d\t%d\t%d\t%d\n" % (k + 1, palette[k, 0], palette[k, 1], palette[k, 2]))
     return out

@@ -21,50 +21,9 @@ import os
 
 import numpy as np
 
-MAX_STATES = 64              # phmrf_smooth_labels: K <= 64 (u8 labels, 64-bin vote histograms)
+from .maps import MAX_STATES, check_len_vec, check_state_vec, default_max_area, device, regions, stem
+
 RATIO = 0.5                  # read_state_test.m's call of query_neighbor_state_test (fixed in the kernel: 2 count > total)
-
-
-def default_max_area(H):
-    """read_state_test.m: threshold 80, or 25 when the region's height (len_vec column 4) is < 100"""
-    return 25 if int(H) < 100 else 80
-
-
-def _integral(a, what):
-    a = np.asarray(a)
-    if a.dtype.kind in "iu":
-        return a.astype(np.int64)
-    if a.dtype.kind == "f" and a.size and np.all(np.isfinite(a)) and np.all(a == np.round(a)):
-        return a.astype(np.int64)
-    if a.dtype.kind == "f" and a.size == 0:
-        return a.astype(np.int64)
-    raise ValueError("%s must hold integers (got dtype %s)" % (what, a.dtype))
-
-
-def check_state_vec(state_vec):
-    """-> the states as int64 [n] (any shape with one non-singleton axis; a .mat file stores them as 1 x n)"""
-    s = _integral(state_vec, "state_vec").reshape(-1)
-    if s.size and (s.min() < 0 or s.max() >= MAX_STATES):
-        raise ValueError("state_vec must hold states in [0, %d) (got %d .. %d)" % (MAX_STATES, s.min(), s.max()))
-    return s
-
-
-def check_len_vec(len_vec, n_states):
-    """-> len_vec as int64 [regions, >= 10]; every region a consistent slice of a state_vec of n_states entries"""
-    L = _integral(np.atleast_2d(len_vec), "len_vec")
-    if L.ndim != 2 or L.shape[1] < 10 or L.shape[0] < 1:
-        raise ValueError("len_vec must have rows of at least 10 columns (got shape %s)" % (L.shape,))
-    for r, row in enumerate(L):
-        n, a, b, H, W, diag = (int(x) for x in row[[0, 1, 2, 3, 4, 8]])
-        if H < 1 or W < 1 or diag not in (0, 1) or (diag == 1 and H != W):
-            raise ValueError("len_vec row %d: H = %d, W = %d, type %d is not a region" % (r, H, W, diag))
-        want = H * (H + 1) // 2 if diag else H * W
-        if not (0 <= a <= b <= n_states) or b - a != want or n != want:
-            raise ValueError("len_vec row %d: [%d, %d) with n = %d does not hold the %d nodes of a %s %d x %d region of a "
-                             "state_vec of %d" % (r, a, b, n, want, "diagonal" if diag else "off-diagonal", H, W, n_states))
-        if row[5] < 0 or row[6] < 0:
-            raise ValueError("len_vec row %d: negative start bin" % r)
-    return L
 
 
 def smooth_states(state_vec, len_vec, window=5, max_area=None, n_iter=1):
@@ -82,21 +41,17 @@ def smooth_states(state_vec, len_vec, window=5, max_area=None, n_iter=1):
         raise ValueError("max_area must be >= 0 (None: the reference's 80 / 25 rule)")
     from . import _lib
     import torch
-    lib = _lib.load()
-    _lib.require_gpu()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    stream = torch.cuda.current_stream(dev).cuda_stream
+    lib, dev, stream = device()
     out = states.astype(np.uint8)
     counts = np.zeros((L.shape[0], n_iter, 3), dtype=np.int64)
-    for r, row in enumerate(L):
-        a, b, H, W, diag = int(row[1]), int(row[2]), int(row[3]), int(row[4]), int(row[8])
+    for r, a, b, H, W, diag, _ in regions(L):
         area = default_max_area(H) if max_area is None else int(max_area)
         K = int(out[a:b].max()) + 1
         src = torch.from_numpy(out[a:b].copy()).to(dev)
         dst = torch.empty_like(src)
         c = np.zeros(3 * max(n_iter, 1), dtype=np.int64)
         _lib.check(lib.phmrf_smooth_labels(ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()), H, W, diag, K,
-                                           window, area, n_iter, _lib.ptr_i64(c), ctypes.c_void_p(stream)))
+                                           window, area, n_iter, _lib.ptr_i64(c), stream))
         out[a:b] = dst.cpu().numpy()
         counts[r] = c[:3 * n_iter].reshape(n_iter, 3)
         del src, dst
@@ -178,8 +133,7 @@ def postprocess_file(mat_path, output_path, resolution, window=5, max_area=None,
     write_state_files(state_vec, len_vec, resolution, output_path, "ori")
     write_state_files(smooth, len_vec, resolution, output_path, "smooth")
     areas = np.array([default_max_area(r[3]) if max_area is None else int(max_area) for r in len_vec], dtype=np.int64)
-    stem = os.path.splitext(os.path.basename(mat_path))[0]
-    out = os.path.join(output_path, "smooth_%s.mat" % stem)
+    out = os.path.join(output_path, "smooth_%s.mat" % stem(mat_path))
     scipy.io.savemat(out, {"state_vec": state_vec, "state_vec_smooth": smooth, "len_vec": len_vec,
                            "smooth_window": int(window), "smooth_area": areas, "smooth_iter": int(n_iter),
                            "smooth_counts": counts, "resolution": int(resolution)})

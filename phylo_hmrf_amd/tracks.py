@@ -17,8 +17,7 @@ import os
 
 import numpy as np
 
-from .compare import _device, _stem
-from .smooth import MAX_STATES, check_len_vec, check_state_vec
+from .maps import MAX_STATES, check_len_vec, check_state_vec, device, load_map, regions, stem
 
 GRID_CAP = 1024                  # csrc/tracks.hip TRACKS_GRID_CAP: workgroups (of 256 lanes) of its kernel
 TILE_H = 32                      # csrc/tracks.hip TRACKS_TILE_H: storage rows of the tile a workgroup counts at a time ...
@@ -112,16 +111,15 @@ def state_tracks(state_vec, len_vec, windows=((0, -1),), K=None):
     K = (int(s.max()) + 1 if s.size else 1) if K is None else int(K)
     if K < 1 or K > MAX_STATES:
         raise ValueError("K must be in 1 .. %d" % MAX_STATES)
-    lib, dev, stream = _device()
+    lib, dev, stream = device()
     s_t = torch.from_numpy(s.astype(np.uint8)).to(dev)
     Q = wins.shape[0]
     out, rows, cols = {}, [], []
-    for r, row in enumerate(L):
-        lo, hi, H, W, diag = int(row[1]), int(row[2]), int(row[3]), int(row[4]), int(row[8])
+    for r, lo, hi, H, W, diag, dist0 in regions(L):
         rr = np.zeros((Q, H, K), dtype=np.int64)
         cc = None if diag else np.zeros((Q, W, K), dtype=np.int64)
         for q, (d_min, d_max) in enumerate(wins):
-            _lib.check(lib.phmrf_state_tracks(ctypes.c_void_p(s_t[lo:hi].data_ptr()), H, W, diag, int(row[6]) - int(row[5]), K,
+            _lib.check(lib.phmrf_state_tracks(ctypes.c_void_p(s_t[lo:hi].data_ptr()), H, W, diag, dist0, K,
                                               int(d_min), int(d_max), _lib.ptr_i64(rr[q]),
                                               None if diag else _lib.ptr_i64(cc[q]), stream))
         rows.append(rr)
@@ -188,7 +186,6 @@ def tracks_files(path, output_path, resolution, field="state_vec", windows_bp="0
     """The command line's --tracks: project the `field` of one estimate_ou_*.mat / segment_*.mat / smooth_*.mat.  Writes under
     output_path tracks_<stem>.npz (state_tracks' arrays, len_vec, resolution, tracks_field, windows_bp; no pickles) and per
     window q tracks_<stem>_w<q>.txt (track_lines).  -> the .npz"""
-    from .domains import load_map
     res = int(resolution)
     if res < 1:
         raise ValueError("resolution must be >= 1")
@@ -196,11 +193,11 @@ def tracks_files(path, output_path, resolution, field="state_vec", windows_bp="0
     s, L, _ = load_map(path, field)
     tracks = state_tracks(s, L, windows=wins)
     os.makedirs(output_path, exist_ok=True)
-    stem = _stem(path)
-    out = os.path.join(output_path, "tracks_%s.npz" % stem)
+    name = stem(path)
+    out = os.path.join(output_path, "tracks_%s.npz" % name)
     np.savez(out, len_vec=L, resolution=np.int64(res), tracks_field=np.array(field), windows_bp=np.array(str(windows_bp)),
              **tracks)
     for q in range(len(wins)):
-        with open(os.path.join(output_path, "tracks_%s_w%d.txt" % (stem, q)), "wb") as fh:
+        with open(os.path.join(output_path, "tracks_%s_w%d.txt" % (name, q)), "wb") as fh:
             fh.write("".join(track_lines(tracks, L, res, q)).encode())
     return out

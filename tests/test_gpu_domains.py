@@ -310,6 +310,58 @@ def test_state_one_of_a_two_state_map_against_the_differential_domains(gpu, H, W
     assert np.array_equal(ones[:, :7], old[:found.value, :7])
 
 
+def _islands(H, W):
+    """state-1 rectangles of 1 - 6 rows and columns, one per cell of an 8 x 8 lattice and two cells of state 0 apart, so every
+    one is a component: about sixty of them.  The ones in the lattice's diagonal cells cross the diagonal (a diagonal block:
+    their own mirrors), the others lie clear of it (mirror twins).  One is a single node, one has a hole of a single node of
+    state 0."""
+    rng = np.random.default_rng(H * W)
+    M = np.zeros((H, W), dtype=np.int64)
+    for a in range(0, H - 7, 8):
+        for b in range(0, W - 7, 8):
+            h, w = rng.integers(1, 7, 2)
+            M[a + 1:a + 1 + h, b + 1:b + 1 + w] = 1
+    M[1:7, 25:31] = 0
+    M[3, 27] = 1                                            # a single node, off the diagonal
+    M[9:14, 33:38] = 1
+    M[11, 35] = 0                                           # a hole: a single-node component of state 0
+    return M
+
+
+@pytest.mark.parametrize("H,W,diag", [(65, 65, True), (64, 65, False)])
+def test_smoothing_comparison_and_domains_list_the_same_components(gpu, H, W, diag):
+    """The three calls take their areas and the ids of their listed roots from one piece of code (csrc/components.h):
+    the areas and node counts of state 1's domains are those of the differential domains of the map against zeros, and the
+    smoothing's count of small components at max_area = A is the number of domains of either state with area <= A."""
+    from phylo_hmrf_amd import _lib
+    L, dev, st = gpu
+    s = _nodes(_islands(H, W), diag)
+    s_t, z_t = _put(dev, s), _put(dev, np.zeros_like(s))
+    status, table, found, _, _, _ = _domains(gpu, s, H, W, diag, 2)
+    assert status == 0 and found == table.shape[0] > 30
+    ones, area, nodes = table[table[:, 7] == 1], table[:, 6], table[:, 5]
+    assert (nodes == 1).sum() >= 2 and set(table[nodes == 1, 7]) == {0, 1}                # the single nodes of either state
+    if diag:
+        assert (ones[:, 6] > ones[:, 5]).sum() >= 5 and (ones[:, 6] == ones[:, 5]).sum() >= 20   # own mirrors, mirror twins
+
+    old = np.full((s.size, 12), FILL, dtype=np.int64)
+    n_old = ctypes.c_int64(FILL)
+    assert L.phmrf_diff_domains(ctypes.c_void_p(s_t.data_ptr()), ctypes.c_void_p(z_t.data_ptr()), None, None, None, H, W,
+                                int(diag), 0, 2, 2, 0.0, 1, None, s.size, _lib.ptr_i64(old), ctypes.byref(n_old), None, st) == 0
+    assert n_old.value == ones.shape[0]
+    assert np.array_equal(old[:n_old.value, 5], ones[:, 5]) and np.array_equal(old[:n_old.value, 6], ones[:, 6])
+
+    out_t = _put(dev, np.zeros_like(s))
+    small = []
+    for A in (0, 1, 2, 8, 20, 36, 50, int(area.max())):
+        counts = np.full(3, FILL, dtype=np.int64)
+        assert L.phmrf_smooth_labels(ctypes.c_void_p(s_t.data_ptr()), ctypes.c_void_p(out_t.data_ptr()), H, W, int(diag), 2, 5, A,
+                                     1, _lib.ptr_i64(counts), st) == 0
+        assert counts[0] == (area <= A).sum(), (A, counts[0], (area <= A).sum())
+        small.append(int(counts[0]))
+    assert small[0] == 0 and small[-1] == found and len(set(small)) >= 6
+
+
 # ---- end to end -------------------------------------------------------------------------------------------------------------
 def _two_regions():
     rng = np.random.default_rng(21)

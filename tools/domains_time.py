@@ -41,7 +41,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-KERNELS = ("domains_", "cc_", "__amd_rocclr")       # the call's kernels in a trace: its own, the union-find, the memsets
+KERNELS = ("domains_", "components_", "cc_", "__amd_rocclr")   # the call's kernels in a trace: its own, csrc/components.h's, the union-find, the memsets
 NOT_MEASURED = ["the adjacency kernel's own time (the kernel pass makes domain calls only)", "bytes moved and the share of the HBM peak",
                 "state_domains end to end (host -> device, the calls, device -> host)", "maps with confidences",
                 "other shares than --share, other K than the workload's", "the spread between runs (the fastest of --repeats counts)"]

@@ -9,7 +9,7 @@ uniformly drawn state).  Printed as one JSON line, in milliseconds:
     write_ori, write_smooth   write_state_files of the input and of the smoothed states (--out, removed afterwards)
 
 The kernels' own times come from a kernel trace: rocprofv3 --kernel-trace --stats -- python tools/smooth_time.py --no-write
-(smooth_*_kernel and the cc_*_grid / cc_flatten kernels of the components).
+(smooth_*_kernel, the components_* kernels of csrc/components.h and the cc_*_grid / cc_flatten kernels of the union-find).
 """
 import argparse
 import ctypes
