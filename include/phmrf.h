@@ -517,6 +517,30 @@ PHMRF_API int phmrf_pair_enrichment(const uint8_t* labels_dev, int H, int W, int
                                     int64_t* obs_host /* [2*C*C*K] */, int64_t* state_dist_host /* [D*K] */,
                                     int64_t* cat_dist_host /* [D*2*C*C] */, void* hip_stream);
 
+/* phmrf_state_pileup: the state map of ONE region piled up around a list of centres (no block, no ABI
+ * bump).  The full matrix M is the H x W block itself, or for a diagonal block the symmetric matrix M[i][j] = the stored node
+ * (min(i, j), max(i, j)), as in phmrf_render_states; labels in the node order of phmrf_smooth_labels.  A centre is
+ * (ci, cj, orient) in coordinates LOCAL to the region; they may lie outside [0, H) x [0, W) and be negative: the window is
+ * clipped, and a centre whose window misses the region adds nothing.  orient is in 0 .. 3, bit 0 = flip, bit 1 = transpose.
+ * A pile cell (u, v) with u, v in [-w, w] is stored at [u + w][v + w]; with (p, q) = (v, u) if transpose else (u, v) and
+ * s = -1 if flip else +1 it reads the matrix cell (ci + s p, cj + s q); a cell outside the matrix is not counted.
+ *   group_offsets_host  host int64 [G + 1]: the centres of group g are the entries [offsets[g], offsets[g + 1]) of the three
+ *                       device arrays ci_dev, cj_dev (int32) and orient_dev_or_null (u8; NULL: every orient is 0)
+ *   obs_host            host int64 [G][2w + 1][2w + 1][K], written in full: obs[g][u + w][v + w][k] = the centres of group g
+ *                       whose pile cell (u, v) lies on a matrix cell in state k
+ * Centres are not deduplicated, and every matrix cell counts once per centre whose window holds it: this is a read of the
+ * full matrix, no mirror-twin bookkeeping applies.  A matrix cell that no window holds is never inspected: a label >= K
+ * there is no error.  No centres at all: zeros and PHMRF_OK.  Queued on hip_stream, returns when done.  Integers only: the
+ * same bytes from run to run.
+ * PHMRF_ERR_INVALID (nothing written) for a NULL labels_dev, group_offsets_host or obs_host, NULL centre arrays with centres,
+ * H < 1, W < 1, a non-square diagonal block, K < 1, w < 0, G < 1, offsets that do not start at 0 or that decrease, an
+ * orient > 3, or a matrix cell inside some centre's window whose label is >= K; PHMRF_ERR_UNSUPPORTED (nothing written) for
+ * K > 64, w > 64, G > 16, n >= 2^31 - 64, 2^31 centres or more, or a centre coordinate with |c| >= 2^30. */
+PHMRF_API int phmrf_state_pileup(const uint8_t* labels_dev, int H, int W, int diagonal, int K, int w, int G,
+                                 const int64_t* group_offsets_host /* [G+1] */, const int32_t* ci_dev, const int32_t* cj_dev,
+                                 const uint8_t* orient_dev_or_null /* NULL: all 0 */,
+                                 int64_t* obs_host /* [G][2w+1][2w+1][K] */, void* hip_stream);
+
 /* ---- profiling the states ------------------------------------------------------------------------- */
 /* What a state IS, from the block's resident f32 observations x (the uploaded float64 rounded to nearest) and its current
  * labels (no ABI bump: the calls only add entry points).  Both calls run over the nodes the block OWNS

@@ -153,6 +153,21 @@ def parse_args(argv=None):
                       "limit); the default 0- is every distance")
     parser.add_option("--enrich_segments", default="0", help="--enrich: 1 = every line of --enrich_bed is a segment of its own "
                       "(a TAD list): bin pairs inside one interval are counted apart from pairs across intervals")
+    parser.add_option("--pileup", default="", help="skip loading data and fitting: pile the states of this .mat up around the "
+                      "anchors of --pileup_bed or the anchor pairs of --pileup_bedpe (the state counts per cell of a window of "
+                      "+- --pileup_flank around every anchor, summed over the anchors of a name); writes pileup_<stem>.npz, "
+                      "pileup_<stem>.txt and one pileup_<stem>_<name>.png per name under --output (--resolution gives the bin size)")
+    parser.add_option("--pileup_bed", default="", help="--pileup: a BED file `chrom start stop [name [score [strand]]]` with at "
+                      "most 8 distinct names; the piles are centred on the diagonal and flipped for strand -")
+    parser.add_option("--pileup_bedpe", default="", help="--pileup: a BEDPE file `chrom1 start1 stop1 chrom2 start2 stop2 [name]`; "
+                      "the piles are centred on the pairs of the two midpoints")
+    parser.add_option("--pileup_field", default="state_vec", help="--pileup: state_vec or state_vec_smooth")
+    parser.add_option("--pileup_flank", default="1000000", help="--pileup: the window reaches this many bp to either side of an "
+                      "anchor (at most 64 bins)")
+    parser.add_option("--pileup_shift", default="0", help="--pileup: also pile up controls, every anchor shifted by this many bp "
+                      "(a whole number of bins) along the diagonal in both directions; 0: no controls")
+    parser.add_option("--pileup_colors", default="", help="--pileup: a text file of R G B rows (0 .. 255), one per state, in "
+                      "place of the built-in palette")
     parser.add_option("-h", "--help", action="help")
     opts, _ = parser.parse_args(argv)
     return opts
@@ -412,6 +427,32 @@ def check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments,
     return wins[0]
 
 
+def check_pileup(pileup, pileup_bed, pileup_bedpe, pileup_field, pileup_flank, pileup_shift, resolution, segment, postprocess,
+                 compare, domains, render, tracks, enrich, ancestral, save_model, profile, filter_device):
+    """--pileup FILE.mat with --pileup_bed FILE or --pileup_bedpe FILE reads one finished state map and a list of anchors: it
+    goes with nothing that loads data or fits, and with no other reader of a state map -> (the flank, the shift) in bins, or
+    None"""
+    if not pileup:
+        if pileup_bed or pileup_bedpe:
+            raise SystemExit("--pileup_bed and --pileup_bedpe go with --pileup: the .mat to pile up")
+        return None
+    if bool(pileup_bed) == bool(pileup_bedpe):
+        raise SystemExit("--pileup takes its anchors from --pileup_bed or from --pileup_bedpe: exactly one of the two")
+    for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
+                        ("--render", render), ("--tracks", tracks), ("--enrich", enrich), ("--ancestral", ancestral),
+                        ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
+                        ("--filter_device 1", str(filter_device) == "1")):
+        if value:
+            raise SystemExit("--pileup cannot be combined with %s: it loads no data and fits nothing" % name)
+    if pileup_field not in ("state_vec", "state_vec_smooth"):
+        raise SystemExit("--pileup_field must be state_vec or state_vec_smooth, not %r" % (pileup_field,))
+    from phylo_hmrf_amd.pileup import check_bins
+    try:
+        return check_bins(int(resolution), int(pileup_flank), int(pileup_shift))
+    except ValueError as e:
+        raise SystemExit("--pileup with --pileup_flank %s and --pileup_shift %s: %s" % (pileup_flank, pileup_shift, e))
+
+
 def run(num_states, chromvec, root_path, multiple, species_name, sort_states, run_id1, cons_param, method_mode,
         initial_mode, initial_weight, initial_weight1, initial_magnitude, position1, position2, filter_sigma, beta,
         beta1, num_neighbor, filter_mode, conv_threshold, estimate_type, simu_version, annotation, reload_mode,
@@ -422,7 +463,11 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
         compare_min_conf="0", compare_area="-1", profile="0", profile_quantiles="0.003,0.25,0.5,0.75,0.997",
         domains="", domains_field="state_vec", domains_area="-1", render="", render_field="state_vec", render_side="2048",
         render_colors="", render_outline="0", render_conf="0", render_mark="", tracks="", tracks_field="state_vec",
-        tracks_dist="0-", enrich="", enrich_bed="", enrich_field="state_vec", enrich_dist="0-", enrich_segments="0"):
+        tracks_dist="0-", enrich="", enrich_bed="", enrich_field="state_vec", enrich_dist="0-", enrich_segments="0",
+        pileup="", pileup_bed="", pileup_bedpe="", pileup_field="state_vec", pileup_flank="1000000", pileup_shift="0",
+        pileup_colors=""):
+    check_pileup(pileup, pileup_bed, pileup_bedpe, pileup_field, pileup_flank, pileup_shift, resolution, segment, postprocess,
+                 compare or compare_with, domains, render, tracks, enrich, ancestral, save_model, profile, filter_device)
     check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments, resolution, segment, postprocess,
                  compare or compare_with, domains, render, tracks, ancestral, save_model, profile, filter_device)
     check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment, postprocess, compare or compare_with, domains,
@@ -441,6 +486,12 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
     if filter_device and (int(reload_mode) == 1 or int(synthetic) > 0 or postprocess):
         raise SystemExit("--filter_device 1 runs the raw loader's filter on the GPU: it cannot be combined with --reload 1, "
                          "--synthetic or --postprocess, where nothing is filtered")
+    if pileup:
+        from phylo_hmrf_amd.pileup import pileup_files
+        out = pileup_files(pileup, str(output_path), int(resolution), field=pileup_field, bed=pileup_bed, bedpe=pileup_bedpe,
+                           flank_bp=int(pileup_flank), shift_bp=int(pileup_shift), palette_path=pileup_colors)
+        print("pile-up written: %s" % out)
+        return out
     if enrich:
         from phylo_hmrf_amd.enrich import enrich_files
         out = enrich_files(enrich, enrich_bed, str(output_path), int(resolution), field=enrich_field, window_bp=enrich_dist,
@@ -657,4 +708,6 @@ if __name__ == "__main__":
         render_outline=opts.render_outline, render_conf=opts.render_conf, render_mark=opts.render_mark,
         tracks=opts.tracks, tracks_field=opts.tracks_field, tracks_dist=opts.tracks_dist, enrich=opts.enrich,
         enrich_bed=opts.enrich_bed, enrich_field=opts.enrich_field, enrich_dist=opts.enrich_dist,
-        enrich_segments=opts.enrich_segments)
+        enrich_segments=opts.enrich_segments, pileup=opts.pileup, pileup_bed=opts.pileup_bed, pileup_bedpe=opts.pileup_bedpe,
+        pileup_field=opts.pileup_field, pileup_flank=opts.pileup_flank, pileup_shift=opts.pileup_shift,
+        pileup_colors=opts.pileup_colors)

@@ -24,7 +24,7 @@ import os
 
 import numpy as np
 
-from .maps import MAX_STATES, check_len_vec, check_state_vec, device, load_map, stem
+from .maps import MAX_STATES, check_len_vec, check_state_vec, chrom_of, device, load_map, stem
 from .tracks import check_windows, covered_bins, parse_windows
 
 GRID_CAP = 1024                  # csrc/enrich.hip ENRICH_GRID_CAP: workgroups (of 256 lanes) of its kernels
@@ -81,9 +81,7 @@ def fold_pairs(table, C):
     return out
 
 
-def _chrom_of(text):
-    t = text[3:] if text.startswith("chr") else text
-    return int(t) if t.isdigit() else None
+_chrom_of = chrom_of
 
 
 def read_annotation(path, len_vec, resolution, segments=False):

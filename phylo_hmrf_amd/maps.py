@@ -1,4 +1,4 @@
-"""What the post-processing modules share (smooth, compare, domains, tracks, render, enrich): the checks of a state map and
+"""What the post-processing modules share (smooth, compare, domains, tracks, render, enrich, pileup): the checks of a state map and
 its regions, the walk over the regions, the GPU handle and the protocol of the calls that list rows.  Host only apart from
 `device()`.
 
@@ -73,6 +73,12 @@ def conf_array(conf, n, what):
 
 def stem(path):
     return os.path.splitext(os.path.basename(path))[0]
+
+
+def chrom_of(text):
+    """the chromosome number of `chr<N>` or `<N>` in an annotation file (len_vec's column 9), None for any other name"""
+    t = text[3:] if text.startswith("chr") else text
+    return int(t) if t.isdigit() else None
 
 
 def load_map(path, field="state_vec"):
