@@ -255,9 +255,23 @@ PHMRF_API int phmrf_block_tile_get_boundary(phmrf_block_t b, uint8_t* top_out, u
 PHMRF_API int phmrf_block_tile_put_halo(phmrf_block_t b, const uint8_t* top_in, const uint8_t* bottom_in);
 /* One colour-ordered ICM sweep / one sweep of one chain family / one component-move pass (exposed
  * for move-level parity tests against oracle/mrf_moves.py).  family: 0 rows, 1 columns,
- * 2 diagonals, 3 anti-diagonals. */
+ * 2 diagonals, 3 anti-diagonals; on a block without a grid: one of the four path families, which are built at the first
+ * call that needs them (once per graph, as at the first solve).  A chain sweep runs the family's cut phase 0 and then its
+ * cut phase 1, each over all the family's colours. */
 PHMRF_API int phmrf_mrf_icm_sweep(phmrf_block_t b, double beta, int64_t* changed);
 PHMRF_API int phmrf_mrf_chain_sweep(phmrf_block_t b, double beta, int family, int64_t* changed);
+/* Read back the chain families (tests; copies from the device and waits for the block's stream).  Entry points added
+ * without an ABI bump, as phmrf_mrf_chain_sweep's reach was widened to blocks without a grid: nothing an older caller relies on
+ * changed.
+ * phmrf_block_chain_family_info: *n_families (0 for a graph of fewer than two nodes without a grid) and, where n_colours is
+ * not NULL, the colours of each of up to four families (0 past the last).
+ * phmrf_block_get_chain_segments: what one launch of the chain kernel -- (family, phase 0 or 1, colour) -- is given:
+ * *n_segments and *n_nodes come back first (the other pointers may be NULL); seg_start / seg_len int32 [*n_segments] are the
+ * position in `nodes` of each segment's first node and its length, nodes int32 [*n_nodes] is the family's node list
+ * (shared by all its launches). */
+PHMRF_API int phmrf_block_chain_family_info(phmrf_block_t b, int* n_families, int* n_colours /*[4] or NULL*/);
+PHMRF_API int phmrf_block_get_chain_segments(phmrf_block_t b, int family, int phase, int colour, int64_t* n_segments,
+                                             int64_t* n_nodes, int32_t* seg_start, int32_t* seg_len, int32_t* nodes);
 PHMRF_API int phmrf_mrf_component_pass(phmrf_block_t b, double beta, int64_t* changed);
 /* ABI 123 (round 6): one alpha-expansion of the WHOLE graph -- every node keeps its label or takes alpha -- by an exact
  * minimum s-t cut on the device (maxflow.hip: lock-free push-relabel with global relabelling, capacities quantised with the

@@ -234,11 +234,10 @@ def solve(g, unary, init, beta, H=None, W=None, diagonal=None, num_neighbor=8, m
 # ------------------------------------------------------------------------------------------------
 # connected-component relabel moves (model of csrc/moves.hip: component pass)
 # ------------------------------------------------------------------------------------------------
-def component_pass(g, unary, labels, beta, margin=True):
-    """Relabel whole connected components of equal label: for every component C and label k the exact
-    dE = sum_{i in C}(u_i(k) - u_i(cur)) - beta * sum_{boundary edges to label k} w; a component moves to its
-    best strictly-improving label unless an adjacent candidate component has a better gain (ties: lower
-    root id).  In place; returns the number of relabelled nodes."""
+def component_table(g, unary, labels, beta):
+    """The move table of the component pass -> (U[nc, K], comp0[n] component of each node, root_of[nc]):
+    U[C, k] = sum_{i in C} u_i(k) - beta * sum_{boundary edges of C to label k} w; root_of = smallest node id of the
+    component (what the device's min-propagation converges to)."""
     import scipy.sparse as sp
     from scipy.sparse.csgraph import connected_components
     K = unary.shape[1]
@@ -246,7 +245,6 @@ def component_pass(g, unary, labels, beta, margin=True):
     same = labels[a] == labels[b]
     A = sp.coo_matrix((np.ones(int(same.sum())), (a[same], b[same])), shape=(g.n, g.n))
     nc, comp0 = connected_components(A, directed=False)
-    # root id = smallest node id of the component (what the device's min-propagation converges to)
     root_of = np.full(nc, g.n, dtype=np.int64)
     np.minimum.at(root_of, comp0, np.arange(g.n))
     U = np.zeros((nc, K))
@@ -254,6 +252,18 @@ def component_pass(g, unary, labels, beta, margin=True):
     cs, cd = comp0[g.src], comp0[g.col]
     bd = cs != cd
     np.add.at(U, (cs[bd], labels[g.col[bd]]), -beta * g.wgt[bd])
+    return U, comp0, root_of
+
+
+def component_pass(g, unary, labels, beta, margin=True):
+    """Relabel whole connected components of equal label: for every component C and label k the exact
+    dE = sum_{i in C}(u_i(k) - u_i(cur)) - beta * sum_{boundary edges to label k} w; a component moves to its
+    best strictly-improving label unless an adjacent candidate component has a better gain (ties: lower
+    root id).  In place; returns the number of relabelled nodes."""
+    U, comp0, root_of = component_table(g, unary, labels, beta)
+    nc = U.shape[0]
+    cs, cd = comp0[g.src], comp0[g.col]
+    bd = cs != cd
     cur = np.zeros(nc, dtype=np.int64)
     cur[comp0] = labels
     tc = U[np.arange(nc), cur]

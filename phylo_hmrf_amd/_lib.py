@@ -97,6 +97,8 @@ SIGNATURES = {
     "phmrf_block_tile_put_halo": [_vp, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8)],
     "phmrf_mrf_icm_sweep": [_vp, _d, _lp],
     "phmrf_mrf_chain_sweep": [_vp, _d, _i, _lp],
+    "phmrf_block_chain_family_info": [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i)],
+    "phmrf_block_get_chain_segments": [_vp, _i, _i, _i, _lp, _lp, _ip, _ip, _ip],
     "phmrf_mrf_component_pass": [_vp, _d, _lp],
     "phmrf_mrf_graph_expansion": [_vp, _d, _i, _lp],
     "phmrf_block_prepare_components": [_vp],

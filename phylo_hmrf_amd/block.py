@@ -221,6 +221,24 @@ class Block(object):
         check(self._L.phmrf_mrf_chain_sweep(self._h, float(beta), int(family), ctypes.byref(c)))
         return c.value
 
+    def chain_family_info(self):
+        """-> the colours of every chain family (grid: rows, columns[, diagonals, anti-diagonals]; no grid: the path families)"""
+        nf = ctypes.c_int(0)
+        ncol = (ctypes.c_int * 4)()
+        check(self._L.phmrf_block_chain_family_info(self._h, ctypes.byref(nf), ncol))
+        return [ncol[f] for f in range(nf.value)]
+
+    def chain_segments(self, family, phase, colour):
+        """the segments of one launch of the chain kernel -> (seg_start int32 [nseg], seg_len int32 [nseg], nodes int32: the
+        family's node list the starts point into) (tests)"""
+        nseg, nn = ctypes.c_int64(0), ctypes.c_int64(0)
+        args = (self._h, int(family), int(phase), int(colour), ctypes.byref(nseg), ctypes.byref(nn))
+        check(self._L.phmrf_block_get_chain_segments(*args, None, None, None))
+        start, length = np.empty(nseg.value, dtype=np.int32), np.empty(nseg.value, dtype=np.int32)
+        nodes = np.empty(nn.value, dtype=np.int32)
+        check(self._L.phmrf_block_get_chain_segments(*args, ptr_i32(start), ptr_i32(length), ptr_i32(nodes)))
+        return start, length, nodes
+
     def prepare_components(self):
         """Queue the labels-only part of the next component pass (connected components of equal label) on the block's
         stream -- between two E-steps, while the host runs the M-step.  A hint: the pass checks on the device that the labels

@@ -194,6 +194,7 @@ int setup_grid_tables(phmrf_block* b, const Geometry& g, int num_neighbor) {
     f.n_chains = C;
     f.n_colours = ncol;
     f.max_len = max_len;
+    f.n_nodes = n;
     PHMRF_TRY(dev_alloc(&f.nodes, (size_t)n));
     PHMRF_TRY(upload(f.nodes, order.data(), (size_t)n * sizeof(int32_t), b->stream));
     for (int phase = 0; phase < 2; ++phase)
@@ -338,6 +339,7 @@ int setup_path_families(phmrf_block* b) {
           ++f.n_chains;
         }
       if (order.empty()) order.push_back(0);
+      f.n_nodes = (int64_t)order.size();
       PHMRF_TRY(dev_alloc(&f.nodes, order.size()));
       PHMRF_TRY(upload(f.nodes, order.data(), order.size() * sizeof(int32_t), b->stream));
       for (int phase = 0; phase < 2; ++phase)
@@ -787,8 +789,12 @@ int phmrf_block_set_grid(phmrf_block_t b, int H, int W, int diagonal, int num_ne
       }
   }
   PHMRF_TRY(setup_grid_tables(b, g, num_neighbor));
-  // kernels that find their neighbours by geometry and COUNT them (the posterior kernel: isolated nodes, estimate_type
-  // != 3) need every stencil edge to be on file; weights alone are indifferent to a missing edge (it weighs 0)
+  // An edge list that is a subset of the stencil is accepted.  Whatever reads WEIGHTS is indifferent to a missing edge (it
+  // weighs 0: the forward-edge records of the strip, coarse and table kernels, the chain links, the adjacency rows).  What
+  // reasons from the SHAPE of the stencil is switched off by grid_complete = false: the component kernels by geometry and
+  // the stencil shortcut of cc_union_kernel (a linked-left node leaving unions to its run-mate: launch_cc runs the
+  // adjacency-row kernels without it), and the kernels that COUNT their neighbours by geometry (the posterior kernel:
+  // isolated nodes, estimate_type != 3).
   b->grid_complete = present == expected;
   return PHMRF_OK;
 }
@@ -1064,15 +1070,51 @@ int phmrf_mrf_icm_sweep(phmrf_block_t b, double beta, int64_t* changed) {
   return read_counter(b, changed);
 }
 
+// a graph without grid geometry gets its path families at its first use, as at its first solve (solve.hip)
+static int ensure_chain_families(phmrf_block* b) {
+  if (!b->has_grid && b->families.empty() && b->nbr && b->n >= 2) PHMRF_TRY(setup_path_families(b));
+  return PHMRF_OK;
+}
+
 int phmrf_mrf_chain_sweep(phmrf_block_t b, double beta, int family, int64_t* changed) {
   PHMRF_TRY(check_solvable(b));
   b->labels_are_slot = 0;
-  PHMRF_CHECK(b->has_grid, PHMRF_ERR_STATE, "chain moves need phmrf_block_set_grid");
+  PHMRF_TRY(ensure_chain_families(b));
   PHMRF_CHECK(family >= 0 && family < (int)b->families.size(), PHMRF_ERR_INVALID, "no such chain family");
   PHMRF_TRY(zero_counter(b));
   PHMRF_TRY(chain_sweep_nocount(b, (float)beta, family, 0));
   PHMRF_TRY(chain_sweep_nocount(b, (float)beta, family, 1));
   return read_counter(b, changed);
+}
+
+int phmrf_block_chain_family_info(phmrf_block_t b, int* n_families, int* n_colours) {
+  PHMRF_CHECK(b && n_families, PHMRF_ERR_INVALID, "NULL argument");
+  PHMRF_CHECK(b->has_graph, PHMRF_ERR_STATE, "graph not set");
+  PHMRF_CHECK(!b->ss, PHMRF_ERR_STATE, "a solve is in progress");
+  PHMRF_TRY(ensure_chain_families(b));
+  *n_families = (int)b->families.size();
+  if (n_colours)
+    for (int f = 0; f < MAX_CHAIN_FAMILIES; ++f) n_colours[f] = f < (int)b->families.size() ? b->families[f].n_colours : 0;
+  return PHMRF_OK;
+}
+
+int phmrf_block_get_chain_segments(phmrf_block_t b, int family, int phase, int colour, int64_t* n_segments, int64_t* n_nodes,
+                                   int32_t* seg_start, int32_t* seg_len, int32_t* nodes) {
+  PHMRF_CHECK(b && n_segments && n_nodes, PHMRF_ERR_INVALID, "NULL argument");
+  PHMRF_CHECK(b->has_graph, PHMRF_ERR_STATE, "graph not set");
+  PHMRF_CHECK(!b->ss, PHMRF_ERR_STATE, "a solve is in progress");
+  PHMRF_TRY(ensure_chain_families(b));
+  PHMRF_CHECK(family >= 0 && family < (int)b->families.size(), PHMRF_ERR_INVALID, "no such chain family");
+  const ChainFamily& f = b->families[family];
+  PHMRF_CHECK(phase == 0 || phase == 1, PHMRF_ERR_INVALID, "phase must be 0 or 1");
+  PHMRF_CHECK(colour >= 0 && colour < f.n_colours, PHMRF_ERR_INVALID, "no such colour in this chain family");
+  const int nseg = f.nseg[phase][colour];
+  *n_segments = nseg;
+  *n_nodes = f.n_nodes;
+  if (seg_start && nseg > 0) PHMRF_TRY(download(seg_start, f.seg_start[phase][colour], (size_t)nseg * sizeof(int32_t), b->stream));
+  if (seg_len && nseg > 0) PHMRF_TRY(download(seg_len, f.seg_len[phase][colour], (size_t)nseg * sizeof(int32_t), b->stream));
+  if (nodes && f.n_nodes > 0) PHMRF_TRY(download(nodes, f.nodes, (size_t)f.n_nodes * sizeof(int32_t), b->stream));
+  return PHMRF_OK;
 }
 
 int phmrf_block_prepare_components(phmrf_block_t b) {

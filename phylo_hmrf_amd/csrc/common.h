@@ -48,6 +48,7 @@ struct ChainFamily {
   uint16_t* memo[2][3] = {};           // device [nseg]: tick of the segment's last quiet run (0 = none), per solve
                                        //   (slices of phmrf_block::chain_memo, set up by phmrf_mrf_solve)
   int nseg[2][3] = {};
+  int64_t n_nodes = 0;                 // entries of `nodes` (a grid family: n; path families: both decompositions' paths)
   int n_chains = 0;
   int n_colours = 0;
   int max_len = 0;

@@ -171,8 +171,10 @@ __global__ __launch_bounds__(256) void chain_kernel(const float* __restrict__ lo
         int cur = __ffsll((long long)__ballot(m == mmin)) - 1;
         for (int t = len - 1; t >= 1; --t) {
           if (lane == t) newl = cur;
-          const unsigned long long jm = ((unsigned long long)__builtin_amdgcn_readlane(jm_hi, t) << 32) |
-                                        (unsigned long long)__builtin_amdgcn_readlane(jm_lo, t);
+          // (readlane returns an int: through unsigned int, or bit 31 of the low half -- label 31's decision -- is
+          //  sign-extended over the decisions of labels 32 .. 63)
+          const unsigned long long jm = ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane(jm_hi, t) << 32) |
+                                        (unsigned long long)(unsigned int)__builtin_amdgcn_readlane(jm_lo, t);
           if ((jm >> cur) & 1ull) cur = (int)__builtin_amdgcn_readlane(am_v, t);
         }
         if (lane == 0) newl = cur;
@@ -265,7 +267,8 @@ __device__ __forceinline__ int cc_find(int32_t* comp, int x) {
   return x;
 }
 
-// grid != 0 (stencil graphs): a node that is linked left shares its up-left and up neighbours with its left run-mate
+// grid != 0 (COMPLETE stencil graphs: launch_cc passes 0 for a grid block with edges missing, whose run-mate may lack the
+// very edge this argument counts on): a node that is linked left shares its up-left and up neighbours with its left run-mate
 // (they are that mate's up and up-right), so it only has to union with its LARGEST remaining smaller neighbour
 // (up-right in an 8-neighbourhood, up in a 4-neighbourhood).  This removes two thirds of the finds and most of the
 // atomics that would all hit the same pair of roots.
@@ -788,7 +791,9 @@ static int launch_cc(phmrf_block* b, const int* gate) {
     hipLaunchKernelGGL(cc_union_grid_kernel, dim3(g), dim3(256), 0, st, b->comp, n, b->W, b->diagonal, b->labels, gate);
   } else {
     hipLaunchKernelGGL(cc_init_kernel, dim3(g), dim3(256), 0, st, b->comp, n, D, b->nbr, b->labels, gate);
-    hipLaunchKernelGGL(cc_union_kernel, dim3(g), dim3(256), 0, st, b->comp, n, D, b->nbr, b->labels, b->has_grid ? b->num_neighbor : 0, gate);
+    // the stencil shortcut of cc_union_kernel takes the left run-mate's unions for granted: only where no stencil edge is missing
+    const int stencil = b->has_grid && b->grid_complete ? b->num_neighbor : 0;
+    hipLaunchKernelGGL(cc_union_kernel, dim3(g), dim3(256), 0, st, b->comp, n, D, b->nbr, b->labels, stencil, gate);
   }
   hipLaunchKernelGGL(cc_flatten_kernel, dim3(g), dim3(256), 0, st, b->comp, n, b->comp_tab, K, tab64, gate);
   return PHMRF_OK;

@@ -232,7 +232,7 @@ def test_icm_general_graph_greedy_colouring_never_raises_energy():
 
 @pytest.mark.parametrize("H,W,K,diagonal,beta", [_as_before(40, 40, 5, True, 1.0), _as_before(33, 150, 8, False, 1.0),
                                                  _as_before(130, 130, 20, True, 1.0), (40, 40, 5, True, 0.5),
-                                                 (33, 150, 8, False, 2.0)])
+                                                 (33, 150, 8, False, 2.0), (40, 40, 64, True, 1.0), (20, 70, 33, False, 2.0)])
 def test_chain_sweeps_match_move_model(H, W, K, diagonal, beta):
     """A family's sweep (two colours, both segment cuts) ends at the model's energy.  The later colours and cuts start
     from what the earlier ones wrote, so kernel and model must also break exact ties alike: both keep a segment's labelling
