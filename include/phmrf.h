@@ -415,6 +415,38 @@ PHMRF_API int phmrf_diff_domains(const uint8_t* a_dev, const uint8_t* b_dev, con
                                  int64_t* table_host /* [capacity*12] */, int64_t* n_domains,
                                  int64_t* band_counts_host_or_null /* [32*3] */, void* hip_stream);
 
+/* ---- the consensus of several state maps ----------------------------------------------------------- */
+/* M state maps of ONE region, no block (no ABI bump: the call only adds an entry point).  u8 labels on
+ * the device in the node order of phmrf_smooth_labels.  The call is queued on hip_stream (NULL: the null stream), returns
+ * when done and uses integers only: the results are the same bytes from run to run.
+ *
+ * phmrf_label_consensus: labels_host is a HOST array of M device pointers (u8 [n] each, 1 <= M <= PHMRF_CONSENSUS_MAPS);
+ * every map may start at any byte and is read in 4-byte words wherever its own address allows.  Raw state l of map m counts
+ * as renumber[m][l] (renumber_host_or_null: host u8 [M][64]; 255: "not a state of this map"; NULL: the identity; two raw
+ * states may map to one).  Per stored node, with votes[k] = the number of maps whose renumbered state is k:
+ *   consensus = the most voted state, the LOWEST on ties;   support = votes[consensus] (1 .. M)
+ *   consensus_dev          device u8 [n]
+ *   support_dev_or_null    device u8 [n]
+ *   core_dev_or_null       device u8 [n]: the consensus where support >= min_support, else K ("unstable"); must be NULL at
+ *                          K = 64, where no state number is free
+ *   support_hist_host      host int64 [K][M + 1]: the nodes with consensus k and support s
+ *   agree_host             host int64 [M][K][K]: agree[m][c][a] = the nodes with consensus c whose map m holds a
+ *   pair_host              host int64 [M][M]: the nodes on which maps m and m' hold the same renumbered state (symmetric, n
+ *                          on the diagonal)
+ *   bands_host             host int64 [PHMRF_DIFF_BANDS][3]: per band of the distance d = |dist0 + j - i| (as
+ *                          phmrf_diff_domains) the nodes, those with support >= min_support and the unanimous ones
+ * Every STORED node counts once (a diagonal block's mirror twins are not doubled: phmrf_label_contingency's convention).
+ * PHMRF_ERR_INVALID, with nothing written on the host or the device, for a NULL required pointer, M < 1, K < 1, min_support
+ * outside [1, M], a non-square diagonal block, a distance of 2^31 or more, K = 64 with a core plane, a raw label >= 64 or a
+ * renumbered state that is 255 or >= K; PHMRF_ERR_UNSUPPORTED for M > 16, K > 64 or n >= 2^31 - 64. */
+#define PHMRF_CONSENSUS_MAPS 16
+PHMRF_API int phmrf_label_consensus(const uint8_t* const* labels_host /* [M] device pointers */, int M,
+                                    const uint8_t* renumber_host_or_null /* [M][64] */, int K, int H, int W, int diagonal,
+                                    int64_t dist0, int min_support, uint8_t* consensus_dev /* [n] */,
+                                    uint8_t* support_dev_or_null /* [n] */, uint8_t* core_dev_or_null /* [n] */,
+                                    int64_t* support_hist_host /* [K*(M+1)] */, int64_t* agree_host /* [M*K*K] */,
+                                    int64_t* pair_host /* [M*M] */, int64_t* bands_host /* [32*3] */, void* hip_stream);
+
 /* ---- the domains of one state map ------------------------------------------------------------------ */
 /* ONE state map of ONE region, no block (no ABI bump: the calls only add entry points).  u8 labels on
  * the device in the node order of phmrf_smooth_labels.  Both calls are queued on hip_stream (NULL: the null stream), return

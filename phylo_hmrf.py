@@ -168,6 +168,18 @@ def parse_args(argv=None):
                       "(a whole number of bins) along the diagonal in both directions; 0: no controls")
     parser.add_option("--pileup_colors", default="", help="--pileup: a text file of R G B rows (0 .. 255), one per state, in "
                       "place of the built-in palette")
+    parser.add_option("--consensus", default="", help="skip loading data and fitting: vote on the state maps of these .mat "
+                      "files, A.mat,B.mat,... (2 .. 16 files on the same regions: repeated fits, or one model's segmentations of "
+                      "several replicates); writes consensus_<stem of the first>_<M>.mat (the most voted state per bin pair, "
+                      "the lowest on ties, with conf = the vote share: a state map every other mode reads), consensus_<...>.txt "
+                      "and consensus_domains_<...>.txt under --output (--resolution gives the bin size)")
+    parser.add_option("--consensus_field", default="state_vec", help="--consensus: state_vec or state_vec_smooth")
+    parser.add_option("--consensus_match", default="0", help="--consensus: 1 = renumber the states of every later file to the "
+                      "first file's by the assignment with the largest agreement (separate fits)")
+    parser.add_option("--consensus_support", default="-1", help="--consensus: a bin pair is stable when this many files hold "
+                      "its consensus state; -1: the strict majority")
+    parser.add_option("--consensus_area", default="-1", help="--consensus: list the stable domains of at least this area in "
+                      "bin pairs; -1: --domains_area's rule")
     parser.add_option("-h", "--help", action="help")
     opts, _ = parser.parse_args(argv)
     return opts
@@ -295,13 +307,13 @@ def check_ancestral(ancestral, segment, postprocess):
                          "its segmentation")
 
 
-def check_profile(profile, profile_quantiles, postprocess, compare):
+def check_profile(profile, profile_quantiles, postprocess, compare, consensus=""):
     """--profile 1 needs the observations on the GPU: it goes with a fit or --segment -> the quantiles, or None when off"""
     if str(profile) not in ("0", "1"):
         raise SystemExit("--profile must be 0 or 1")
     if str(profile) == "0":
         return None
-    for name, value in (("--postprocess", postprocess), ("--compare", compare)):
+    for name, value in (("--postprocess", postprocess), ("--compare", compare), ("--consensus", consensus)):
         if value:
             raise SystemExit("--profile 1 cannot be combined with %s, which loads no data: the profile needs the observations"
                              % name)
@@ -325,14 +337,15 @@ def write_profile(model, state_vec, quantiles, output_path, run_id, K, species, 
 
 
 def check_compare(compare, compare_with, compare_field, compare_match, segment, postprocess, ancestral, save_model,
-                  filter_device):
+                  filter_device, consensus=""):
     """--compare A.mat --compare_with B.mat reads two finished state maps: it goes with nothing that loads data or fits"""
     if not compare and not compare_with:
         return
     if not compare or not compare_with:
         raise SystemExit("--compare and --compare_with go together: the two .mat files to compare")
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--ancestral", ancestral),
-                        ("--save_model", save_model), ("--filter_device 1", str(filter_device) == "1")):
+                        ("--save_model", save_model), ("--filter_device 1", str(filter_device) == "1"),
+                        ("--consensus", consensus)):
         if value:
             raise SystemExit("--compare cannot be combined with %s: it loads no data and fits nothing" % name)
     if compare_field not in ("state_vec", "state_vec_smooth"):
@@ -341,13 +354,14 @@ def check_compare(compare, compare_with, compare_field, compare_match, segment, 
         raise SystemExit("--compare_match must be 0 or 1")
 
 
-def check_domains(domains, domains_field, segment, postprocess, compare, ancestral, save_model, profile, filter_device):
+def check_domains(domains, domains_field, segment, postprocess, compare, ancestral, save_model, profile, filter_device,
+                  consensus=""):
     """--domains FILE.mat reads one finished state map: it goes with nothing that loads data or fits"""
     if not domains:
         return
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare),
                         ("--ancestral", ancestral), ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
-                        ("--filter_device 1", str(filter_device) == "1")):
+                        ("--filter_device 1", str(filter_device) == "1"), ("--consensus", consensus)):
         if value:
             raise SystemExit("--domains cannot be combined with %s: it loads no data and fits nothing" % name)
     if domains_field not in ("state_vec", "state_vec_smooth"):
@@ -355,13 +369,13 @@ def check_domains(domains, domains_field, segment, postprocess, compare, ancestr
 
 
 def check_render(render, render_field, render_side, render_outline, render_conf, segment, postprocess, compare, domains,
-                 ancestral, save_model, profile, filter_device):
+                 ancestral, save_model, profile, filter_device, consensus=""):
     """--render FILE.mat reads one finished state map: it goes with nothing that loads data or fits -> the side, or None"""
     if not render:
         return None
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
                         ("--ancestral", ancestral), ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
-                        ("--filter_device 1", str(filter_device) == "1")):
+                        ("--filter_device 1", str(filter_device) == "1"), ("--consensus", consensus)):
         if value:
             raise SystemExit("--render cannot be combined with %s: it loads no data and fits nothing" % name)
     if render_field not in ("state_vec", "state_vec_smooth"):
@@ -379,14 +393,15 @@ def check_render(render, render_field, render_side, render_outline, render_conf,
 
 
 def check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment, postprocess, compare, domains, ancestral,
-                 save_model, profile, filter_device):
+                 save_model, profile, filter_device, consensus=""):
     """--tracks FILE.mat reads one finished state map: it goes with nothing that loads data or fits -> the windows in bins,
     or None"""
     if not tracks:
         return None
     for name, value in (("--render", render), ("--segment", segment), ("--postprocess", postprocess), ("--compare", compare),
                         ("--domains", domains), ("--ancestral", ancestral), ("--save_model", save_model),
-                        ("--profile 1", str(profile) == "1"), ("--filter_device 1", str(filter_device) == "1")):
+                        ("--profile 1", str(profile) == "1"), ("--filter_device 1", str(filter_device) == "1"),
+                        ("--consensus", consensus)):
         if value:
             raise SystemExit("--tracks cannot be combined with %s: it loads no data and fits nothing" % name)
     if tracks_field not in ("state_vec", "state_vec_smooth"):
@@ -399,7 +414,7 @@ def check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment,
 
 
 def check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments, resolution, segment, postprocess, compare,
-                 domains, render, tracks, ancestral, save_model, profile, filter_device):
+                 domains, render, tracks, ancestral, save_model, profile, filter_device, consensus=""):
     """--enrich FILE.mat --enrich_bed FILE reads one finished state map and an annotation: it goes with nothing that loads data
     or fits, and with no other reader of a state map -> the window (d_min, d_max) in bins, or None"""
     if not enrich:
@@ -410,7 +425,8 @@ def check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments,
         raise SystemExit("--enrich and --enrich_bed go together: the .mat and its annotation file")
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
                         ("--render", render), ("--tracks", tracks), ("--ancestral", ancestral), ("--save_model", save_model),
-                        ("--profile 1", str(profile) == "1"), ("--filter_device 1", str(filter_device) == "1")):
+                        ("--profile 1", str(profile) == "1"), ("--filter_device 1", str(filter_device) == "1"),
+                        ("--consensus", consensus)):
         if value:
             raise SystemExit("--enrich cannot be combined with %s: it loads no data and fits nothing" % name)
     if enrich_field not in ("state_vec", "state_vec_smooth"):
@@ -428,7 +444,7 @@ def check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments,
 
 
 def check_pileup(pileup, pileup_bed, pileup_bedpe, pileup_field, pileup_flank, pileup_shift, resolution, segment, postprocess,
-                 compare, domains, render, tracks, enrich, ancestral, save_model, profile, filter_device):
+                 compare, domains, render, tracks, enrich, ancestral, save_model, profile, filter_device, consensus=""):
     """--pileup FILE.mat with --pileup_bed FILE or --pileup_bedpe FILE reads one finished state map and a list of anchors: it
     goes with nothing that loads data or fits, and with no other reader of a state map -> (the flank, the shift) in bins, or
     None"""
@@ -441,7 +457,7 @@ def check_pileup(pileup, pileup_bed, pileup_bedpe, pileup_field, pileup_flank, p
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
                         ("--render", render), ("--tracks", tracks), ("--enrich", enrich), ("--ancestral", ancestral),
                         ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
-                        ("--filter_device 1", str(filter_device) == "1")):
+                        ("--filter_device 1", str(filter_device) == "1"), ("--consensus", consensus)):
         if value:
             raise SystemExit("--pileup cannot be combined with %s: it loads no data and fits nothing" % name)
     if pileup_field not in ("state_vec", "state_vec_smooth"):
@@ -451,6 +467,38 @@ def check_pileup(pileup, pileup_bed, pileup_bedpe, pileup_field, pileup_flank, p
         return check_bins(int(resolution), int(pileup_flank), int(pileup_shift))
     except ValueError as e:
         raise SystemExit("--pileup with --pileup_flank %s and --pileup_shift %s: %s" % (pileup_flank, pileup_shift, e))
+
+
+def check_consensus(consensus, consensus_field, consensus_match, consensus_support, consensus_area, segment, postprocess,
+                    compare, domains, render, tracks, enrich, pileup, ancestral, save_model, profile, filter_device):
+    """--consensus A.mat,B.mat,... reads finished state maps of the same regions: it goes with nothing that loads data or
+    fits, and with no other reader of a state map -> (the files, min_support or None, min_area or None), or None"""
+    if not consensus:
+        return None
+    for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
+                        ("--render", render), ("--tracks", tracks), ("--enrich", enrich), ("--pileup", pileup),
+                        ("--ancestral", ancestral), ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
+                        ("--filter_device 1", str(filter_device) == "1")):
+        if value:
+            raise SystemExit("--consensus cannot be combined with %s: it loads no data and fits nothing" % name)
+    from phylo_hmrf_amd.consensus import CONSENSUS_MAPS
+    files = [f for f in str(consensus).split(",") if f]
+    if not 2 <= len(files) <= CONSENSUS_MAPS:
+        raise SystemExit("--consensus takes 2 .. %d .mat files separated by commas, not %d" % (CONSENSUS_MAPS, len(files)))
+    if consensus_field not in ("state_vec", "state_vec_smooth"):
+        raise SystemExit("--consensus_field must be state_vec or state_vec_smooth, not %r" % (consensus_field,))
+    if str(consensus_match) not in ("0", "1"):
+        raise SystemExit("--consensus_match must be 0 or 1")
+    try:
+        support, area = int(consensus_support), int(consensus_area)
+    except ValueError:
+        raise SystemExit("--consensus_support and --consensus_area must be integers")
+    if support != -1 and not 1 <= support <= len(files):
+        raise SystemExit("--consensus_support must be -1 (the majority) or lie in [1, %d], the number of files, not %d"
+                         % (len(files), support))
+    if area != -1 and area < 1:
+        raise SystemExit("--consensus_area must be -1 (--domains_area's rule) or >= 1, not %d" % area)
+    return files, None if support == -1 else support, None if area == -1 else area
 
 
 def run(num_states, chromvec, root_path, multiple, species_name, sort_states, run_id1, cons_param, method_mode,
@@ -465,20 +513,26 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
         render_colors="", render_outline="0", render_conf="0", render_mark="", tracks="", tracks_field="state_vec",
         tracks_dist="0-", enrich="", enrich_bed="", enrich_field="state_vec", enrich_dist="0-", enrich_segments="0",
         pileup="", pileup_bed="", pileup_bedpe="", pileup_field="state_vec", pileup_flank="1000000", pileup_shift="0",
-        pileup_colors=""):
+        pileup_colors="", consensus="", consensus_field="state_vec", consensus_match="0", consensus_support="-1",
+        consensus_area="-1"):
+    vote = check_consensus(consensus, consensus_field, consensus_match, consensus_support, consensus_area, segment, postprocess,
+                           compare or compare_with, domains, render, tracks, enrich, pileup, ancestral, save_model, profile,
+                           filter_device)
     check_pileup(pileup, pileup_bed, pileup_bedpe, pileup_field, pileup_flank, pileup_shift, resolution, segment, postprocess,
-                 compare or compare_with, domains, render, tracks, enrich, ancestral, save_model, profile, filter_device)
+                 compare or compare_with, domains, render, tracks, enrich, ancestral, save_model, profile, filter_device,
+                 consensus=consensus)
     check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments, resolution, segment, postprocess,
-                 compare or compare_with, domains, render, tracks, ancestral, save_model, profile, filter_device)
+                 compare or compare_with, domains, render, tracks, ancestral, save_model, profile, filter_device,
+                 consensus=consensus)
     check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment, postprocess, compare or compare_with, domains,
-                 ancestral, save_model, profile, filter_device)
+                 ancestral, save_model, profile, filter_device, consensus=consensus)
     side = check_render(render, render_field, render_side, render_outline, render_conf, segment, postprocess,
-                        compare or compare_with, domains, ancestral, save_model, profile, filter_device)
+                        compare or compare_with, domains, ancestral, save_model, profile, filter_device, consensus=consensus)
     check_domains(domains, domains_field, segment, postprocess, compare or compare_with, ancestral, save_model, profile,
-                  filter_device)
-    profile_q = check_profile(profile, profile_quantiles, postprocess, compare)
+                  filter_device, consensus=consensus)
+    profile_q = check_profile(profile, profile_quantiles, postprocess, compare, consensus=consensus)
     check_compare(compare, compare_with, compare_field, compare_match, segment, postprocess, ancestral, save_model,
-                  filter_device)
+                  filter_device, consensus=consensus)
     check_ancestral(ancestral, segment, postprocess)
     filter_device = int(filter_device)
     if filter_device not in (0, 1):
@@ -486,6 +540,13 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
     if filter_device and (int(reload_mode) == 1 or int(synthetic) > 0 or postprocess):
         raise SystemExit("--filter_device 1 runs the raw loader's filter on the GPU: it cannot be combined with --reload 1, "
                          "--synthetic or --postprocess, where nothing is filtered")
+    if vote:
+        from phylo_hmrf_amd.consensus import consensus_files
+        files, support, area = vote
+        out = consensus_files(files, str(output_path), int(resolution), field=consensus_field, match=bool(int(consensus_match)),
+                              min_support=support, min_area=area)
+        print("consensus written: %s" % out)
+        return out
     if pileup:
         from phylo_hmrf_amd.pileup import pileup_files
         out = pileup_files(pileup, str(output_path), int(resolution), field=pileup_field, bed=pileup_bed, bedpe=pileup_bedpe,
@@ -710,4 +771,5 @@ if __name__ == "__main__":
         enrich_bed=opts.enrich_bed, enrich_field=opts.enrich_field, enrich_dist=opts.enrich_dist,
         enrich_segments=opts.enrich_segments, pileup=opts.pileup, pileup_bed=opts.pileup_bed, pileup_bedpe=opts.pileup_bedpe,
         pileup_field=opts.pileup_field, pileup_flank=opts.pileup_flank, pileup_shift=opts.pileup_shift,
-        pileup_colors=opts.pileup_colors)
+        pileup_colors=opts.pileup_colors, consensus=opts.consensus, consensus_field=opts.consensus_field,
+        consensus_match=opts.consensus_match, consensus_support=opts.consensus_support, consensus_area=opts.consensus_area)

@@ -114,6 +114,7 @@ SIGNATURES = {
     "phmrf_smooth_labels": [_vp, _vp, _i, _i, _i, _i, _i, _i64, _i, _lp, _vp],
     "phmrf_label_contingency": [_vp, _vp, _i64, _i, _i, _lp, _vp],
     "phmrf_diff_domains": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i, _i, ctypes.c_float, _i64, _vp, _i64, _lp, _lp, _lp, _vp],
+    "phmrf_label_consensus": [_vp, _i, _vp, _i, _i, _i, _i, _i64, _i, _vp, _vp, _vp, _lp, _lp, _lp, _lp, _vp],
     "phmrf_state_adjacency": [_vp, _i, _i, _i, _i, _lp, _vp],
     "phmrf_state_domains": [_vp, _vp, _i, _i, _i, _i64, _i, _i64, _vp, _i64, _lp, _lp, _lp, _vp],
     "phmrf_render_states": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp],
