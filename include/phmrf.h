@@ -124,6 +124,14 @@ PHMRF_API int phmrf_block_get_saved_labels(phmrf_block_t b, int slot, int32_t* l
  * nothing is evaluated: *e_current = +inf, *e_saved = 0. */
 PHMRF_API int phmrf_block_warm_start(phmrf_block_t b, double beta, int slot, int choose, double* e_current, double* e_saved,
                                      int* took_saved);
+/* The number behind the unreported choice (no ABI bump: the call only adds an entry point): out[0] = unary part, out[1] =
+ * beta x pair part of E(current labels) - E(snapshot in `slot`), summed over the nodes where the two labellings differ
+ * (a node or one of its four forward neighbours), over the rows the block OWNS if it is a row tile.  Reads only; waits for
+ * the block's stream.  Always that one kernel, at every size, and never two full passes instead: PHMRF_ERR_UNSUPPORTED on a
+ * block without grid geometry, PHMRF_ERR_STATE while the label-major unary planes are not current (a strip pass or a solve
+ * builds them after phmrf_block_set_logprob; phmrf_emission writes them once they exist), for an empty slot or without
+ * labels.  In deterministic mode the sums are formed in the 2^-20 fixed point of every energy evaluation. */
+PHMRF_API int phmrf_block_energy_diff(phmrf_block_t b, double beta, int slot, double* out /*[2]*/);
 
 /* ---- b1: emission ---------------------------------------------------------------------------- */
 /* logprob[i,k] = log N(x_i; means[k], covars[k]) for all nodes of the block, left resident in HBM.
@@ -706,8 +714,10 @@ PHMRF_API int phmrf_block_get_work(phmrf_block_t b, int64_t* out /*[8]*/);
  * round is the full sweep of both orientations, the later rounds revisit the strips whose inputs changed -- the two kinds of
  * launch a roofline figure has to keep apart (bench.py: roofline.full_sweep / roofline.mop_up). */
 PHMRF_API int phmrf_block_get_work_first(phmrf_block_t b, int64_t* out /*[8]*/);
-/* ABI 122 (round 6): the same ten-entry form of both (first_round_only != 0: the _first part); min(capacity, 10) entries.
- * Entries 0..7 as above; entries 8 and 9 always read 0 (no kernel counts into them; the layout stays ten entries wide).  */
+/* ABI 122 (round 6): the wider form of both (first_round_only != 0: the _first part); min(capacity, 11) entries.
+ * Entries 0..7 as above; entries 8 and 9 always read 0 (no kernel counts into them).  Entry 10 (a caller with capacity 10
+ * never sees it; 0 in the _first part): the energy evaluations of solve rounds that took the incremental pass -- the
+ * change on the nodes the round's moves stamped, added to the previous evaluation -- instead of the full one.  */
 PHMRF_API int phmrf_block_get_work_ex(phmrf_block_t b, int first_round_only, int capacity, int64_t* out /*[capacity]*/);
 /* The timed intervals of one kernel class on a time base common to all blocks of the calling thread's device
  * (phmrf_time_base_reset marks t = 0; call it before the timed region): out = [start_ms, end_ms] pairs, at most

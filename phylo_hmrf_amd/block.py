@@ -100,6 +100,14 @@ class Block(object):
                                              ctypes.byref(es), ctypes.byref(took)))
         return ec.value, es.value, bool(took.value)
 
+    def energy_diff(self, beta, slot):
+        """E(current labels) - E(snapshot in `slot`) -> (unary part, beta x pair part), from the nodes where the two differ
+        (include/phmrf.h, phmrf_block_energy_diff: the kernel behind warm_start(report=False), at any size; a row tile counts
+        the rows it owns).  Raises where that kernel cannot run: no grid geometry, or unary planes that are not current."""
+        out = np.zeros(2, dtype=np.float64)
+        check(self._L.phmrf_block_energy_diff(self._h, float(beta), int(slot), ptr_d(out)))
+        return float(out[0]), float(out[1])
+
     def get_saved_labels(self, slot):
         out = np.empty(self.n, dtype=np.int32)
         check(self._L.phmrf_block_get_saved_labels(self._h, slot, ptr_i32(out)))
@@ -424,6 +432,13 @@ class Block(object):
         out = (ctypes.c_int64 * 10)()
         check(self._L.phmrf_block_get_work_ex(self._h, 0, 10, out))
         return dict(zip(self._WORK_KEYS, out))
+
+    def incremental_energies(self):
+        """Energy evaluations of solve rounds since reset_timing that added the change on the touched nodes to the previous
+        evaluation instead of passing over the block again (entry 10 of phmrf_block_get_work_ex)."""
+        out = (ctypes.c_int64 * 11)()
+        check(self._L.phmrf_block_get_work_ex(self._h, 0, 11, out))
+        return int(out[10])
 
     def work_first(self):
         """The part of work() done in the first round of every solve (a warm start's full sweeps) since reset_timing."""

@@ -1023,7 +1023,7 @@ int phmrf_block_warm_start(phmrf_block_t b, double beta, int slot, int choose, d
     return PHMRF_OK;
   }
   double* const extra = b->accum + (ACCUM_DOUBLES - 4);     // (behind every statistic the accum area can hold)
-  if (choose && !report && energy_diff_available(b)) {
+  if (choose && !report && b->n >= (1 << 16) && energy_diff_available(b)) {
     // nobody asked for the two energies: what decides is the SIGN of their difference, which comes from the nodes where the
     // two labellings differ (energy_diff_grid_kernel) -- one light pass instead of two full ones; the choice kernel then
     // compares (difference, 0)
@@ -1059,6 +1059,29 @@ int phmrf_block_warm_start(phmrf_block_t b, double beta, int slot, int choose, d
   if (e_current) *e_current = cur;
   if (e_saved) *e_saved = sav;
   if (took_saved) *took_saved = !(cur < sav) ? 1 : 0;
+  return PHMRF_OK;
+}
+
+// E(current labels) - E(snapshot) as a number, from the nodes where the two differ: the kernel behind the unreported warm
+// start, at any size (the size gate is phmrf_block_warm_start's own).  Never another way: where the kernel cannot run the
+// call says so.
+int phmrf_block_energy_diff(phmrf_block_t b, double beta, int slot, double* out) {
+  PHMRF_TRY(check_solvable(b));
+  PHMRF_CHECK(out, PHMRF_ERR_INVALID, "NULL argument");
+  PHMRF_CHECK(slot >= 0 && slot < 4 && b->saved[slot], PHMRF_ERR_STATE, "label slot is empty");
+  PHMRF_CHECK(b->has_labels, PHMRF_ERR_STATE, "labels not set");
+  PHMRF_CHECK(b->has_grid && b->fwd_w && b->H > 0 && b->W > 0, PHMRF_ERR_UNSUPPORTED,
+              "the energy difference from the differing nodes needs a grid block (phmrf_block_set_grid / build_grid_graph)");
+  PHMRF_CHECK(energy_diff_available(b), PHMRF_ERR_STATE,
+              "the unary planes are not current (a strip pass or a solve builds them after phmrf_block_set_logprob)");
+  PHMRF_TRY(zero_accum(b, 4, 2));
+  tic(b, KC_ENERGY);
+  PHMRF_TRY(launch_energy_diff(b, b->saved[slot]));
+  toc(b, KC_ENERGY, 1);
+  PHMRF_HIP(hipMemcpyAsync(b->accum_host + 4, b->accum + 4, 2 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+  PHMRF_HIP(hipStreamSynchronize(b->stream));
+  energy_sums(b, b->accum_host + 4, &out[0], &out[1]);
+  out[1] = beta * out[1];
   return PHMRF_OK;
 }
 
@@ -1559,7 +1582,7 @@ int phmrf_block_reset_timing(phmrf_block_t b) {
     b->ms[i] = b->ms_first[i] = 0;
     b->launches[i] = b->launches_first[i] = 0;
   }
-  for (int q = 0; q < 10; ++q) b->work[q] = b->work_first[q] = 0;
+  for (int q = 0; q < N_WORK; ++q) b->work[q] = b->work_first[q] = 0;
   PHMRF_HIP(hipMemsetAsync(b->work_acc, 0, WORK_BANKS * WORK_SLOTS * sizeof(unsigned long long), b->stream));
   b->intervals.clear();
   return PHMRF_OK;
@@ -1590,7 +1613,7 @@ int phmrf_block_get_work_first(phmrf_block_t b, int64_t* out) {
 
 int phmrf_block_get_work_ex(phmrf_block_t b, int first_round_only, int capacity, int64_t* out) {
   PHMRF_CHECK(b && out, PHMRF_ERR_INVALID, "NULL argument");
-  for (int q = 0; q < 10 && q < capacity; ++q) out[q] = first_round_only ? b->work_first[q] : b->work[q];
+  for (int q = 0; q < N_WORK && q < capacity; ++q) out[q] = first_round_only ? b->work_first[q] : b->work[q];
   return PHMRF_OK;
 }
 

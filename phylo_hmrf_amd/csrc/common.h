@@ -74,6 +74,8 @@ constexpr int COUNTER_COARSE = PHMRF_COUNTER_COARSE;        // + lv: coarse scal
 // development traces of the strip kernels (strips, not labels; a kernel gets the address of counters[COUNTER_TRACE] or null)
 constexpr int COUNTER_TRACE = 100;
 enum TraceCounter { TRACE_SEEN = 0, TRACE_PAST_MEMO = 1, TRACE_INTO_DP = 2, TRACE_DP_STEPS = 3, TRACE_MOVED = 4, N_TRACE = 5 };
+constexpr int N_WORK = 11;                                  // entries of phmrf_block_get_work_ex
+constexpr int WORK_INCREMENTAL = 10;                        //   ... the last: energy evaluations of a solve's rounds that took the incremental pass
 constexpr int COUNTER_ENERGY = 120;                         // [120], [121]: the round's (unary, pair) energy sums (energy_round_launch)
 static_assert(COUNTER_DEFAULT < COUNTER_EXPANSION && COUNTER_EXPANSION + MAX_LABELS <= COUNTER_CHAIN, "label slots run into the chain slots");
 static_assert(COUNTER_CHAIN + MAX_CHAIN_FAMILIES <= COUNTER_ICM && COUNTER_ICM < COUNTER_COMPONENT && COUNTER_COMPONENT < COUNTER_FUSION,
@@ -196,8 +198,8 @@ struct phmrf_block {
   int64_t launches[PHMRF_NUM_KERNEL_CLASSES] = {};
   double ms_first[PHMRF_NUM_KERNEL_CLASSES] = {};           // ... of the launches in the first round of a solve
   int64_t launches_first[PHMRF_NUM_KERNEL_CLASSES] = {};
-  int64_t work_first[10] = {};              //   ... the part of it done in the first round of each solve
-  int64_t work[10] = {};                    // strips staged, their cells, staged cells, DP steps, strip launches, ... (phmrf_block_get_work_ex)
+  int64_t work_first[phmrf::N_WORK] = {};   //   ... the part of it done in the first round of each solve
+  int64_t work[phmrf::N_WORK] = {};         // strips staged, their cells, staged cells, DP steps, strip launches, ... (phmrf_block_get_work_ex)
   struct Interval { int kclass; float t0, t1; };
   std::vector<Interval> intervals;          // resolved timed intervals on the library's common time base (ms)
 

@@ -386,27 +386,30 @@ __global__ __launch_bounds__(256) void energy_grid_kernel(const float* __restric
 // ring), and an edge's term can only differ where an end has changed -- so the touched nodes' unary terms and forward
 // edges, new labelling minus the snapshot `prev` taken at the last evaluation, are the whole difference, term by term exact
 // in f32 and summed in f64.  Waves whose nodes are all untouched read two bytes per node; a mop-up round of a warm solve
-// touches a few per cent of the block.  Same thread layout as energy_grid_kernel.
+// touches a few per cent of the block.  Same thread layout as energy_grid_kernel, and the same rows [row0, row1): a row
+// tile counts the rows it owns -- a halo row's own terms and forward edges are the neighbouring tile's.  The labels a tile
+// RECEIVES for its lower halo row (put_labels_kernel) are a change like any other: the snapshot keeps the halo's labels of
+// the last evaluation and the stamps the kernel writes reach the last owned row, whose edges into the halo are the tile's.
 __global__ __launch_bounds__(256) void energy_delta_grid_kernel(const float* __restrict__ uT, int64_t n, int H, int W, int diagonal,
                                                                 const float4* __restrict__ fwd_w,
                                                                 const uint8_t* __restrict__ labels,
                                                                 const uint8_t* __restrict__ prev,
                                                                 const uint16_t* __restrict__ stamp, int since,
-                                                                double* __restrict__ accum, int det) {
+                                                                double* __restrict__ accum, int det, int row0, int row1) {
   __shared__ double red[8];
   const int j = blockIdx.x * 64 + (threadIdx.x & 63);
   double eu = 0.0, ep = 0.0;
   constexpr int UR = 4;
   const int stride = gridDim.y * 4;
-  const int row_end = (diagonal && blockIdx.x * 64 + 64 < H) ? blockIdx.x * 64 + 64 : H;      // (see energy_grid_kernel)
-  for (int i0 = blockIdx.y * 4 + (threadIdx.x >> 6); i0 < row_end; i0 += stride * UR) {
+  const int row_end = (diagonal && blockIdx.x * 64 + 64 < row1) ? blockIdx.x * 64 + 64 : row1;      // (see energy_grid_kernel)
+  for (int i0 = row0 + blockIdx.y * 4 + (threadIdx.x >> 6); i0 < row_end; i0 += stride * UR) {
     int64_t node[UR];
     bool on[UR];
     bool any = false;
 #pragma unroll
     for (int u = 0; u < UR; ++u) {
       const int i = i0 + u * stride;
-      const bool in = i < H && j < W && !(diagonal && j < i);
+      const bool in = i < row1 && j < W && !(diagonal && j < i);
       node[u] = in ? grid_row_base(i, W, diagonal) + j : 0;
       on[u] = in && (int)stamp[node[u]] > since;
       any = any || on[u];
@@ -1269,8 +1272,9 @@ int launch_choose_labels(const phmrf_block* b, const uint8_t* saved, const doubl
 }
 
 // E(current labels) - E(other) into the block's energy slots (caller zeroes them); grid blocks with unary planes only
+// (at any size: from how many nodes on the one light pass beats two full ones is the caller's business, phmrf_block_warm_start)
 bool energy_diff_available(const phmrf_block* b) {
-  return b->has_grid && b->fwd_w && b->H > 0 && b->W > 0 && b->uT && b->uT_valid && b->n >= (1 << 16);
+  return b->has_grid && b->fwd_w && b->H > 0 && b->W > 0 && b->uT && b->uT_valid;
 }
 
 int launch_energy_diff(const phmrf_block* b, const uint8_t* other) {
@@ -1308,8 +1312,8 @@ int launch_energy(const phmrf_block* b, float beta, double* accum_at) {
   return PHMRF_OK;
 }
 
-// -> accum[ACC_ENERGY .. +1] += the change of (unary, pair) since the snapshot `labels_eval` / tick `eval_tick` (grid blocks
-// with current unary planes only: energy_delta_available)
+// -> accum[ACC_ENERGY .. +1] += the change of (unary, pair) since the snapshot `labels_eval` / tick `eval_tick`, over the rows
+// the block owns (grid blocks with current unary planes only: energy_delta_available)
 bool energy_delta_available(const phmrf_block* b) {
   return b->has_grid && b->fwd_w && b->H > 0 && b->W > 0 && b->uT && b->uT_valid && b->stamp && b->tick > 0 && b->labels_eval &&
          b->eval_tick >= 0;
@@ -1321,8 +1325,9 @@ int launch_energy_delta(const phmrf_block* b, double* accum_at) {
   int gy = (b->H + 3) / 4;
   const int cap = 2048 / gx + 1;
   if (gy > cap) gy = cap;
+  const int row0 = b->own_r1 >= 0 ? b->own_r0 : 0, row1 = b->own_r1 >= 0 ? b->own_r1 : b->H;
   hipLaunchKernelGGL(energy_delta_grid_kernel, dim3(gx, gy), dim3(256), 0, b->stream, b->uT, b->n, b->H, b->W, b->diagonal,
-                     b->fwd_w, b->labels, b->labels_eval, b->stamp, b->eval_tick, acc, b->deterministic ? 1 : 0);
+                     b->fwd_w, b->labels, b->labels_eval, b->stamp, b->eval_tick, acc, b->deterministic ? 1 : 0, row0, row1);
   PHMRF_HIP(hipGetLastError());
   return PHMRF_OK;
 }

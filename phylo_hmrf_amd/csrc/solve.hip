@@ -149,11 +149,17 @@ int coarse_sweep_nocount(phmrf_block* b, float beta, int level, int off, int shi
 // energy_round_collect reads it once the stream has been synchronised.  The first evaluation of a solve is the full pass;
 // later ones on a large grid block add the change since the previous evaluation, taken from the nodes the round's moves have
 // stamped (energy_delta_grid_kernel) -- a mop-up round touches a few per cent of the block.  Each evaluation leaves a
-// snapshot of the labels and its tick behind for the next.  (PHMRF_ENERGY_FULL=1: always the full pass;
-// PHMRF_ENERGY_CHECK=1: both, compared.)  The carried values are (unary, pair without beta).
+// snapshot of the labels and its tick behind for the next.  A row tile counts the rows it owns in both passes; the halo
+// labels it receives between two evaluations (tile.hip, put_labels_kernel) leave the snapshot alone, so the next
+// incremental pass sees them as a change of the tile's edges into its lower halo row.  (Development library:
+// PHMRF_ENERGY_FULL=1: always the full pass; PHMRF_ENERGY_CHECK=1: both, compared, tiles included; PHMRF_ENERGY_MIN_N: the
+// size from which the incremental pass is taken.)  The carried values are (unary, pair without beta).
 static int energy_round_launch(phmrf_block* b, bool* incremental_out, bool* snapshot_out) {
   static const bool always_full = PHMRF_DEV_ENV("PHMRF_ENERGY_FULL") != nullptr;
-  const bool grid = b->has_grid && b->fwd_w && b->uT && b->uT_valid && b->stamp && b->tick > 0 && b->n >= (1 << 18);
+  // (PHMRF_ENERGY_MIN_N, development library: the size from which the incremental pass is taken, for tests at small shapes)
+  static const char* const min_n_env = PHMRF_DEV_ENV("PHMRF_ENERGY_MIN_N");
+  static const int64_t min_n = min_n_env ? std::max<int64_t>(1, std::atoll(min_n_env)) : (int64_t)1 << 18;
+  const bool grid = b->has_grid && b->fwd_w && b->uT && b->uT_valid && b->stamp && b->tick > 0 && b->n >= min_n;
   const bool snapshot = grid && !always_full;
   const bool incremental = snapshot && energy_delta_available(b);
   // (round 6) the round's two energy sums live in the counter bank (COUNTER_ENERGY: two slots, as doubles -- or 2^-20 fixed-point integers
@@ -161,8 +167,12 @@ static int energy_round_launch(phmrf_block* b, bool* incremental_out, bool* snap
   // carries them -- two fills / copies per round fewer than with the accumulator area
   tic(b, KC_ENERGY);
   double* const at = reinterpret_cast<double*>(b->counters + COUNTER_ENERGY);
-  if (incremental) PHMRF_TRY(launch_energy_delta(b, at));
-  else PHMRF_TRY(launch_energy(b, 0.f, at));
+  if (incremental) {
+    PHMRF_TRY(launch_energy_delta(b, at));
+    b->work[WORK_INCREMENTAL] += 1;
+  } else {
+    PHMRF_TRY(launch_energy(b, 0.f, at));
+  }
   toc(b, KC_ENERGY, 1);
   if (is_tile(b))        // (the pin-violation count of a row tile: accum slot 6, tile.hip)
     PHMRF_HIP(hipMemcpyAsync(b->accum_host + 6, b->accum + 6, sizeof(double), hipMemcpyDeviceToHost, b->stream));
@@ -194,7 +204,7 @@ static int energy_round_collect(phmrf_block* b, double beta, bool incremental, d
     PHMRF_TRY(energy_now(b, beta, &fu, &fp));
     const double eu = *eu_carry, ep = beta * *ep_carry;
     const double tol = 1e-9 * std::fabs(fu + fp) + 1e-3;
-    if (!is_tile(b) && (std::fabs(fu - eu) > tol || std::fabs(fp - ep) > tol))
+    if (std::fabs(fu - eu) > tol || std::fabs(fp - ep) > tol)
       fprintf(stderr, "[phmrf energy check] incremental %.6f + %.6f, full %.6f + %.6f (diff %.3e, %.3e)\n", eu, ep, fu, fp,
               eu - fu, ep - fp);
   }

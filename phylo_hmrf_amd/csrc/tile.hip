@@ -57,10 +57,12 @@ __global__ __launch_bounds__(256) void tile_pins_kernel(float* __restrict__ logp
   }
 }
 
-// labels[first .. first + count) <- src; a node whose label changes is stamped with its neighbours (the stamps are dilated)
-// and the energy snapshot follows, so that the change counts as an input of the next round and not as one of its moves.
-__global__ __launch_bounds__(256) void put_labels_kernel(uint8_t* __restrict__ labels, uint8_t* __restrict__ labels_eval,
-                                                         const uint8_t* __restrict__ src, int64_t first, int64_t count, int H, int W,
+// labels[first .. first + count) <- src; a node whose label changes is stamped with its neighbours (the stamps are dilated).
+// The energy snapshot (phmrf_block::labels_eval) is NOT touched: the edges from a tile's last owned row into its lower halo
+// row are the tile's own, so a received label changes the tile's energy, and the next incremental evaluation finds that
+// change on the stamped owned row as the difference between the labels and the snapshot (energy_delta_grid_kernel).
+__global__ __launch_bounds__(256) void put_labels_kernel(uint8_t* __restrict__ labels, const uint8_t* __restrict__ src,
+                                                         int64_t first, int64_t count, int H, int W,
                                                          int diagonal, uint16_t* __restrict__ stamp, int tick,
                                                          uint8_t* __restrict__ pin_label0, int64_t pf0, int64_t pc0,
                                                          uint8_t* __restrict__ pin_label1, int64_t pf1, int64_t pc1) {
@@ -69,7 +71,6 @@ __global__ __launch_bounds__(256) void put_labels_kernel(uint8_t* __restrict__ l
     const uint8_t l = src[q];
     if (labels[v] == l) continue;
     labels[v] = l;
-    if (labels_eval) labels_eval[v] = l;
     if (pin_label0 && v >= pf0 && v < pf0 + pc0) pin_label0[v - pf0] = l;
     if (pin_label1 && v >= pf1 && v < pf1 + pc1) pin_label1[v - pf1] = l;
     if (stamp) {
@@ -110,10 +111,9 @@ int launch_put_labels(phmrf_block* b, int64_t first, int64_t count, const uint8_
   if (count <= 0) return PHMRF_OK;
   int64_t g64 = (count + 255) / 256;
   const int grid = (int)(g64 > 4096 ? 4096 : g64);
-  hipLaunchKernelGGL(put_labels_kernel, dim3(grid), dim3(256), 0, b->stream, b->labels,
-                     (b->tick && b->eval_tick >= 0) ? b->labels_eval : nullptr, src_dev, first, count, b->H, b->W, b->diagonal,
-                     b->tick ? b->stamp : nullptr, b->tick, b->pin_label[0], b->pin_first[0], b->pin_count[0], b->pin_label[1],
-                     b->pin_first[1], b->pin_count[1]);
+  hipLaunchKernelGGL(put_labels_kernel, dim3(grid), dim3(256), 0, b->stream, b->labels, src_dev, first, count, b->H, b->W,
+                     b->diagonal, b->tick ? b->stamp : nullptr, b->tick, b->pin_label[0], b->pin_first[0], b->pin_count[0],
+                     b->pin_label[1], b->pin_first[1], b->pin_count[1]);
   PHMRF_HIP(hipGetLastError());
   return PHMRF_OK;
 }

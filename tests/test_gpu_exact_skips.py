@@ -35,6 +35,9 @@ SKIP_CASES = {
     "rect257x70_k5_nn4": (257, 70, False, 5, 4, 1000, {}, 0),           # the 4-stencil's own dilation pattern
     "tri500_k12_no_expansion": (500, 500, True, 12, 8, 1000, {"use_expansion": False}, 0),   # chain memo live from round 2
     "tri500_k12_three_tiles": (500, 500, True, 12, 8, 1000, {}, 3),     # halo rows arrive from outside the tile
+    # the one case at or above 2^18 nodes, where the product takes the incremental energy from the second round on: here the
+    # arm with PHMRF_ENERGY_FULL differs from the product arm in fact (every smaller block takes the full pass in both)
+    "rect513x513_k5": (513, 513, False, 5, 8, 1000, {}, 0),
 }
 
 SKIP_SCRIPT = r"""
@@ -74,7 +77,8 @@ for name, (H, W, diag, K, nn, tol, extra, parts) in CASES.items():
             b.emission(mu, cv); b.reset_timing()
             res = b.solve(1.0, energy_tol_ppb=tol, init_mode=1 if i == 0 else 0, **extra)
             w = b.work()
-            out.append((sha(b.get_labels()), res["rounds"], res["changed"], repr(res["energy"]), w["units"], w["proposal_nodes"]))
+            out.append((sha(b.get_labels()), res["rounds"], res["changed"], repr(res["energy"]), w["units"], w["proposal_nodes"],
+                        b.incremental_energies()))
         b.close()
     else:
         Xh = X.cpu().numpy().astype(np.float64)
@@ -98,7 +102,7 @@ for name, (H, W, diag, K, nn, tol, extra, parts) in CASES.items():
                 lab[tl.owned_global_slice()] = tl.b.get_labels()[tl.owned_local_slice()]
             w = [tl.b.work() for tl in g.local.values()]
             out.append((sha(lab), res["rounds"], res["changed"], repr(res["energy"]), sum(x["units"] for x in w),
-                        sum(x["proposal_nodes"] for x in w)))
+                        sum(x["proposal_nodes"] for x in w), sum(tl.b.incremental_energies() for tl in g.local.values())))
         for tl in g.local.values():
             tl.b.close()
     del X
@@ -110,7 +114,8 @@ for name, (H, W, diag, K, nn, tol, extra, parts) in CASES.items():
 def skip_arms():
     """Both arms, one child process each (PHMRF_DETERMINISTIC=1): the product library with its skips, and the development
     library with PHMRF_NO_SKIP and PHMRF_ENERGY_FULL (the incremental energy is a skip of its own kind, with its own knob).
-    -> {arm: {case: [(label sha1, rounds, changed, repr(energy), units, proposal_nodes) per solve]}}"""
+    -> {arm: {case: [(label sha1, rounds, changed, repr(energy), units, proposal_nodes, incremental energy evaluations) per
+    solve]}}"""
     dev = os.path.join(ROOT, "phylo_hmrf_amd", "libphmrf_dev.so")      # (the knobs exist in the -DPHMRF_DEV build only)
     assert os.path.exists(dev), "libphmrf_dev.so not built (make -C phylo_hmrf_amd/csrc)"
     script = SKIP_SCRIPT.replace("@CASES@", repr(SKIP_CASES))
@@ -137,7 +142,9 @@ def test_exact_skips_leave_every_labelling_alone(skip_arms, case):
     of changed labels and energy with the memos and the proposal skip (product library) and without them (PHMRF_NO_SKIP).
     Teeth: in every warm solve the arm with the skips stages strictly fewer strips and computes strictly fewer proposals
     than the arm without, so the knob took effect and the skips were exercised; every cold solve runs at least three
-    rounds, every warm solve at least two.
+    rounds, every warm solve at least two.  The incremental energy (energy_round_launch: blocks of 2^18 nodes and more, from
+    a solve's second evaluation on) ran in every solve of such a block in the product arm and in none with
+    PHMRF_ENERGY_FULL; smaller blocks never take it.
 
     Measured on an MI355X (both arms equal in every entry; rounds per solve | strips staged, with skips : without |
     proposals computed, with : without; the test prints them, -s):
@@ -162,6 +169,11 @@ def test_exact_skips_leave_every_labelling_alone(skip_arms, case):
         assert fast[i][1] >= 2, fast
         assert fast[i][4] < slow[i][4], ("units, warm solve %d" % i, fast[i], slow[i])
         assert fast[i][5] < slow[i][5], ("proposal_nodes, warm solve %d" % i, fast[i], slow[i])
+    H, W, diag, parts = SKIP_CASES[case][0], SKIP_CASES[case][1], SKIP_CASES[case][2], SKIP_CASES[case][7]
+    large = not parts and (H * (H + 1) // 2 if diag else H * W) >= 1 << 18
+    for f, s in zip(fast, slow):
+        assert s[6] == 0, ("incremental energy evaluations with PHMRF_ENERGY_FULL", s)
+        assert (f[6] > 0) if large else (f[6] == 0), ("incremental energy evaluations", f)
 
 
 # ------------------------------------------------------------------------------------------------ converged = fixed point
