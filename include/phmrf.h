@@ -595,6 +595,31 @@ PHMRF_API int phmrf_state_pileup(const uint8_t* labels_dev, int H, int W, int di
                                  const uint8_t* orient_dev_or_null /* NULL: all 0 */,
                                  int64_t* obs_host /* [G][2w+1][2w+1][K] */, void* hip_stream);
 
+/* phmrf_rect_states: the state histograms of many rectangles of ONE region (no block, no ABI bump).
+ * Labels in the node order of phmrf_smooth_labels; conf_dev_or_null: float32 per node in the same order.  Rectangle t is
+ * rect_host[t] = (i0, i1, j0, j1) in coordinates LOCAL to the region and holds the stored nodes (i, j) with i0 <= i < i1,
+ * j0 <= j < j1, 0 <= i < H, 0 <= j < W and, in a diagonal block, i <= j: coordinates may be negative or lie beyond the
+ * region (they are clipped), a rectangle with i1 <= i0 or j1 <= j0 holds nothing, and rectangles are not deduplicated.
+ * With sign(t) = -1 where minus_host_or_null[t] is 1 and +1 otherwise, and row(t) = slot_host_or_null[t] (NULL: t itself, and
+ * Q must be R):
+ *   counts_host         host int64 [Q][K], written in full: counts[row(t)][k] += sign(t) (the nodes of rectangle t in state k)
+ *   conf_host_or_null   host int64 [Q], written in full: conf[row(t)] += sign(t) (the sum of (uint64)(conf[v] 2^24) over the
+ *                       nodes v of rectangle t): phmrf_state_domains' fixed point
+ * Both are the signed sums; rows that no rectangle names are 0.  Every stored node counts once per rectangle that holds it:
+ * a diagonal block's mirror twins are not doubled.  A node that no rectangle holds is never inspected: a label >= K or a
+ * bad confidence there is no error.  R = 0: zeros and PHMRF_OK.  Queued on hip_stream, returns when done.  Integers only:
+ * the same bytes from run to run.
+ * PHMRF_ERR_INVALID (nothing written) for a NULL labels_dev or counts_host, a NULL rect_host with R > 0, conf_host_or_null
+ * without conf_dev_or_null, H < 1, W < 1, a non-square diagonal block, K < 1, R < 0, Q < 1, a NULL slot array with Q != R, a
+ * slot outside [0, Q), a minus byte > 1, or a node inside some rectangle whose label is >= K or whose confidence is not a
+ * finite number in [0, 1]; PHMRF_ERR_UNSUPPORTED (nothing written) for K > 64, n >= 2^31 - 64, R >= 2^31, Q K >= 2^31 or a
+ * coordinate with |c| >= 2^30. */
+PHMRF_API int phmrf_rect_states(const uint8_t* labels_dev, const float* conf_dev_or_null, int H, int W, int diagonal, int K,
+                                int64_t R, const int32_t* rect_host /* [R][4]: i0, i1, j0, j1 */,
+                                const int32_t* slot_host_or_null /* [R] */, const uint8_t* minus_host_or_null /* [R] */,
+                                int64_t Q, int64_t* counts_host /* [Q][K] */, int64_t* conf_host_or_null /* [Q] */,
+                                void* hip_stream);
+
 /* ---- profiling the states ------------------------------------------------------------------------- */
 /* What a state IS, from the block's resident f32 observations x (the uploaded float64 rounded to nearest) and its current
  * labels (no ABI bump: the calls only add entry points).  Both calls run over the nodes the block OWNS

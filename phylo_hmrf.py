@@ -180,6 +180,18 @@ def parse_args(argv=None):
                       "its consensus state; -1: the strict majority")
     parser.add_option("--consensus_area", default="-1", help="--consensus: list the stable domains of at least this area in "
                       "bin pairs; -1: --domains_area's rule")
+    parser.add_option("--query", default="", help="skip loading data and fitting: the state composition of this .mat inside every "
+                      "interval of --query_bed (the bin pairs inside a TAD) or between the two intervals of every line of "
+                      "--query_bedpe (a loop, a TAD pair, an enhancer-promoter pair): per line the state counts, the dominant state, "
+                      "its share, the entropy and the mean confidence; writes query_<stem>.npz and query_<stem>.txt under "
+                      "--output (--resolution gives the bin size)")
+    parser.add_option("--query_bed", default="", help="--query: a BED file `chrom start stop [name]`; an interval takes every bin "
+                      "it overlaps")
+    parser.add_option("--query_bedpe", default="", help="--query: a BEDPE file `chrom1 start1 stop1 chrom2 start2 stop2 [name]`, "
+                      "both ends on one chromosome")
+    parser.add_option("--query_field", default="state_vec", help="--query: state_vec or state_vec_smooth")
+    parser.add_option("--query_shift", default="0", help="--query: also count two controls per line, both intervals shifted by "
+                      "this many bp (a whole number of bins) along the diagonal in either direction; 0: no controls")
     parser.add_option("-h", "--help", action="help")
     opts, _ = parser.parse_args(argv)
     return opts
@@ -307,13 +319,13 @@ def check_ancestral(ancestral, segment, postprocess):
                          "its segmentation")
 
 
-def check_profile(profile, profile_quantiles, postprocess, compare, consensus=""):
+def check_profile(profile, profile_quantiles, postprocess, compare, consensus="", query=""):
     """--profile 1 needs the observations on the GPU: it goes with a fit or --segment -> the quantiles, or None when off"""
     if str(profile) not in ("0", "1"):
         raise SystemExit("--profile must be 0 or 1")
     if str(profile) == "0":
         return None
-    for name, value in (("--postprocess", postprocess), ("--compare", compare), ("--consensus", consensus)):
+    for name, value in (("--postprocess", postprocess), ("--compare", compare), ("--consensus", consensus), ("--query", query)):
         if value:
             raise SystemExit("--profile 1 cannot be combined with %s, which loads no data: the profile needs the observations"
                              % name)
@@ -337,7 +349,7 @@ def write_profile(model, state_vec, quantiles, output_path, run_id, K, species, 
 
 
 def check_compare(compare, compare_with, compare_field, compare_match, segment, postprocess, ancestral, save_model,
-                  filter_device, consensus=""):
+                  filter_device, consensus="", query=""):
     """--compare A.mat --compare_with B.mat reads two finished state maps: it goes with nothing that loads data or fits"""
     if not compare and not compare_with:
         return
@@ -345,7 +357,7 @@ def check_compare(compare, compare_with, compare_field, compare_match, segment, 
         raise SystemExit("--compare and --compare_with go together: the two .mat files to compare")
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--ancestral", ancestral),
                         ("--save_model", save_model), ("--filter_device 1", str(filter_device) == "1"),
-                        ("--consensus", consensus)):
+                        ("--consensus", consensus), ("--query", query)):
         if value:
             raise SystemExit("--compare cannot be combined with %s: it loads no data and fits nothing" % name)
     if compare_field not in ("state_vec", "state_vec_smooth"):
@@ -355,13 +367,13 @@ def check_compare(compare, compare_with, compare_field, compare_match, segment, 
 
 
 def check_domains(domains, domains_field, segment, postprocess, compare, ancestral, save_model, profile, filter_device,
-                  consensus=""):
+                  consensus="", query=""):
     """--domains FILE.mat reads one finished state map: it goes with nothing that loads data or fits"""
     if not domains:
         return
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare),
                         ("--ancestral", ancestral), ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
-                        ("--filter_device 1", str(filter_device) == "1"), ("--consensus", consensus)):
+                        ("--filter_device 1", str(filter_device) == "1"), ("--consensus", consensus), ("--query", query)):
         if value:
             raise SystemExit("--domains cannot be combined with %s: it loads no data and fits nothing" % name)
     if domains_field not in ("state_vec", "state_vec_smooth"):
@@ -369,13 +381,13 @@ def check_domains(domains, domains_field, segment, postprocess, compare, ancestr
 
 
 def check_render(render, render_field, render_side, render_outline, render_conf, segment, postprocess, compare, domains,
-                 ancestral, save_model, profile, filter_device, consensus=""):
+                 ancestral, save_model, profile, filter_device, consensus="", query=""):
     """--render FILE.mat reads one finished state map: it goes with nothing that loads data or fits -> the side, or None"""
     if not render:
         return None
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
                         ("--ancestral", ancestral), ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
-                        ("--filter_device 1", str(filter_device) == "1"), ("--consensus", consensus)):
+                        ("--filter_device 1", str(filter_device) == "1"), ("--consensus", consensus), ("--query", query)):
         if value:
             raise SystemExit("--render cannot be combined with %s: it loads no data and fits nothing" % name)
     if render_field not in ("state_vec", "state_vec_smooth"):
@@ -393,7 +405,7 @@ def check_render(render, render_field, render_side, render_outline, render_conf,
 
 
 def check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment, postprocess, compare, domains, ancestral,
-                 save_model, profile, filter_device, consensus=""):
+                 save_model, profile, filter_device, consensus="", query=""):
     """--tracks FILE.mat reads one finished state map: it goes with nothing that loads data or fits -> the windows in bins,
     or None"""
     if not tracks:
@@ -401,7 +413,7 @@ def check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment,
     for name, value in (("--render", render), ("--segment", segment), ("--postprocess", postprocess), ("--compare", compare),
                         ("--domains", domains), ("--ancestral", ancestral), ("--save_model", save_model),
                         ("--profile 1", str(profile) == "1"), ("--filter_device 1", str(filter_device) == "1"),
-                        ("--consensus", consensus)):
+                        ("--consensus", consensus), ("--query", query)):
         if value:
             raise SystemExit("--tracks cannot be combined with %s: it loads no data and fits nothing" % name)
     if tracks_field not in ("state_vec", "state_vec_smooth"):
@@ -414,7 +426,7 @@ def check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment,
 
 
 def check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments, resolution, segment, postprocess, compare,
-                 domains, render, tracks, ancestral, save_model, profile, filter_device, consensus=""):
+                 domains, render, tracks, ancestral, save_model, profile, filter_device, consensus="", query=""):
     """--enrich FILE.mat --enrich_bed FILE reads one finished state map and an annotation: it goes with nothing that loads data
     or fits, and with no other reader of a state map -> the window (d_min, d_max) in bins, or None"""
     if not enrich:
@@ -426,7 +438,7 @@ def check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments,
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
                         ("--render", render), ("--tracks", tracks), ("--ancestral", ancestral), ("--save_model", save_model),
                         ("--profile 1", str(profile) == "1"), ("--filter_device 1", str(filter_device) == "1"),
-                        ("--consensus", consensus)):
+                        ("--consensus", consensus), ("--query", query)):
         if value:
             raise SystemExit("--enrich cannot be combined with %s: it loads no data and fits nothing" % name)
     if enrich_field not in ("state_vec", "state_vec_smooth"):
@@ -444,7 +456,7 @@ def check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments,
 
 
 def check_pileup(pileup, pileup_bed, pileup_bedpe, pileup_field, pileup_flank, pileup_shift, resolution, segment, postprocess,
-                 compare, domains, render, tracks, enrich, ancestral, save_model, profile, filter_device, consensus=""):
+                 compare, domains, render, tracks, enrich, ancestral, save_model, profile, filter_device, consensus="", query=""):
     """--pileup FILE.mat with --pileup_bed FILE or --pileup_bedpe FILE reads one finished state map and a list of anchors: it
     goes with nothing that loads data or fits, and with no other reader of a state map -> (the flank, the shift) in bins, or
     None"""
@@ -457,7 +469,7 @@ def check_pileup(pileup, pileup_bed, pileup_bedpe, pileup_field, pileup_flank, p
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
                         ("--render", render), ("--tracks", tracks), ("--enrich", enrich), ("--ancestral", ancestral),
                         ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
-                        ("--filter_device 1", str(filter_device) == "1"), ("--consensus", consensus)):
+                        ("--filter_device 1", str(filter_device) == "1"), ("--consensus", consensus), ("--query", query)):
         if value:
             raise SystemExit("--pileup cannot be combined with %s: it loads no data and fits nothing" % name)
     if pileup_field not in ("state_vec", "state_vec_smooth"):
@@ -470,7 +482,7 @@ def check_pileup(pileup, pileup_bed, pileup_bedpe, pileup_field, pileup_flank, p
 
 
 def check_consensus(consensus, consensus_field, consensus_match, consensus_support, consensus_area, segment, postprocess,
-                    compare, domains, render, tracks, enrich, pileup, ancestral, save_model, profile, filter_device):
+                    compare, domains, render, tracks, enrich, pileup, ancestral, save_model, profile, filter_device, query=""):
     """--consensus A.mat,B.mat,... reads finished state maps of the same regions: it goes with nothing that loads data or
     fits, and with no other reader of a state map -> (the files, min_support or None, min_area or None), or None"""
     if not consensus:
@@ -478,7 +490,7 @@ def check_consensus(consensus, consensus_field, consensus_match, consensus_suppo
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
                         ("--render", render), ("--tracks", tracks), ("--enrich", enrich), ("--pileup", pileup),
                         ("--ancestral", ancestral), ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
-                        ("--filter_device 1", str(filter_device) == "1")):
+                        ("--filter_device 1", str(filter_device) == "1"), ("--query", query)):
         if value:
             raise SystemExit("--consensus cannot be combined with %s: it loads no data and fits nothing" % name)
     from phylo_hmrf_amd.consensus import CONSENSUS_MAPS
@@ -501,6 +513,31 @@ def check_consensus(consensus, consensus_field, consensus_match, consensus_suppo
     return files, None if support == -1 else support, None if area == -1 else area
 
 
+def check_query(query, query_bed, query_bedpe, query_field, query_shift, resolution, segment, postprocess, compare, domains,
+                render, tracks, enrich, pileup, consensus, ancestral, save_model, profile, filter_device):
+    """--query FILE.mat with --query_bed FILE or --query_bedpe FILE reads one finished state map and a list of intervals: it
+    goes with nothing that loads data or fits, and with no other reader of a state map -> the shift in bins, or None"""
+    if not query:
+        if query_bed or query_bedpe:
+            raise SystemExit("--query_bed and --query_bedpe go with --query: the .mat to look the intervals up in")
+        return None
+    if bool(query_bed) == bool(query_bedpe):
+        raise SystemExit("--query takes its intervals from --query_bed or from --query_bedpe: exactly one of the two")
+    for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
+                        ("--render", render), ("--tracks", tracks), ("--enrich", enrich), ("--pileup", pileup),
+                        ("--consensus", consensus), ("--ancestral", ancestral), ("--save_model", save_model),
+                        ("--profile 1", str(profile) == "1"), ("--filter_device 1", str(filter_device) == "1")):
+        if value:
+            raise SystemExit("--query cannot be combined with %s: it loads no data and fits nothing" % name)
+    if query_field not in ("state_vec", "state_vec_smooth"):
+        raise SystemExit("--query_field must be state_vec or state_vec_smooth, not %r" % (query_field,))
+    from phylo_hmrf_amd.pileup import check_bins
+    try:
+        return check_bins(int(resolution), 0, int(query_shift))[1]
+    except ValueError as e:
+        raise SystemExit("--query with --query_shift %s: %s" % (query_shift, e))
+
+
 def run(num_states, chromvec, root_path, multiple, species_name, sort_states, run_id1, cons_param, method_mode,
         initial_mode, initial_weight, initial_weight1, initial_magnitude, position1, position2, filter_sigma, beta,
         beta1, num_neighbor, filter_mode, conv_threshold, estimate_type, simu_version, annotation, reload_mode,
@@ -514,25 +551,28 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
         tracks_dist="0-", enrich="", enrich_bed="", enrich_field="state_vec", enrich_dist="0-", enrich_segments="0",
         pileup="", pileup_bed="", pileup_bedpe="", pileup_field="state_vec", pileup_flank="1000000", pileup_shift="0",
         pileup_colors="", consensus="", consensus_field="state_vec", consensus_match="0", consensus_support="-1",
-        consensus_area="-1"):
+        consensus_area="-1", query="", query_bed="", query_bedpe="", query_field="state_vec", query_shift="0"):
+    check_query(query, query_bed, query_bedpe, query_field, query_shift, resolution, segment, postprocess,
+                compare or compare_with, domains, render, tracks, enrich, pileup, consensus, ancestral, save_model, profile,
+                filter_device)
     vote = check_consensus(consensus, consensus_field, consensus_match, consensus_support, consensus_area, segment, postprocess,
                            compare or compare_with, domains, render, tracks, enrich, pileup, ancestral, save_model, profile,
-                           filter_device)
+                           filter_device, query=query)
     check_pileup(pileup, pileup_bed, pileup_bedpe, pileup_field, pileup_flank, pileup_shift, resolution, segment, postprocess,
                  compare or compare_with, domains, render, tracks, enrich, ancestral, save_model, profile, filter_device,
-                 consensus=consensus)
+                 consensus=consensus, query=query)
     check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments, resolution, segment, postprocess,
                  compare or compare_with, domains, render, tracks, ancestral, save_model, profile, filter_device,
-                 consensus=consensus)
+                 consensus=consensus, query=query)
     check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment, postprocess, compare or compare_with, domains,
-                 ancestral, save_model, profile, filter_device, consensus=consensus)
+                 ancestral, save_model, profile, filter_device, consensus=consensus, query=query)
     side = check_render(render, render_field, render_side, render_outline, render_conf, segment, postprocess,
-                        compare or compare_with, domains, ancestral, save_model, profile, filter_device, consensus=consensus)
+                        compare or compare_with, domains, ancestral, save_model, profile, filter_device, consensus=consensus, query=query)
     check_domains(domains, domains_field, segment, postprocess, compare or compare_with, ancestral, save_model, profile,
-                  filter_device, consensus=consensus)
-    profile_q = check_profile(profile, profile_quantiles, postprocess, compare, consensus=consensus)
+                  filter_device, consensus=consensus, query=query)
+    profile_q = check_profile(profile, profile_quantiles, postprocess, compare, consensus=consensus, query=query)
     check_compare(compare, compare_with, compare_field, compare_match, segment, postprocess, ancestral, save_model,
-                  filter_device, consensus=consensus)
+                  filter_device, consensus=consensus, query=query)
     check_ancestral(ancestral, segment, postprocess)
     filter_device = int(filter_device)
     if filter_device not in (0, 1):
@@ -546,6 +586,12 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
         out = consensus_files(files, str(output_path), int(resolution), field=consensus_field, match=bool(int(consensus_match)),
                               min_support=support, min_area=area)
         print("consensus written: %s" % out)
+        return out
+    if query:
+        from phylo_hmrf_amd.query import query_files
+        out = query_files(query, str(output_path), int(resolution), field=query_field, bed=query_bed, bedpe=query_bedpe,
+                          shift_bp=int(query_shift))
+        print("query written: %s" % out)
         return out
     if pileup:
         from phylo_hmrf_amd.pileup import pileup_files
@@ -772,4 +818,6 @@ if __name__ == "__main__":
         enrich_segments=opts.enrich_segments, pileup=opts.pileup, pileup_bed=opts.pileup_bed, pileup_bedpe=opts.pileup_bedpe,
         pileup_field=opts.pileup_field, pileup_flank=opts.pileup_flank, pileup_shift=opts.pileup_shift,
         pileup_colors=opts.pileup_colors, consensus=opts.consensus, consensus_field=opts.consensus_field,
-        consensus_match=opts.consensus_match, consensus_support=opts.consensus_support, consensus_area=opts.consensus_area)
+        consensus_match=opts.consensus_match, consensus_support=opts.consensus_support, consensus_area=opts.consensus_area,
+        query=opts.query, query_bed=opts.query_bed, query_bedpe=opts.query_bedpe, query_field=opts.query_field,
+        query_shift=opts.query_shift)

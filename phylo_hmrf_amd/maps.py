@@ -1,5 +1,6 @@
-"""What the post-processing modules share (smooth, compare, domains, tracks, render, enrich, pileup): the checks of a state map and
-its regions, the walk over the regions, the GPU handle and the protocol of the calls that list rows.  Host only apart from
+"""What the post-processing modules share (smooth, compare, domains, tracks, render, enrich, pileup, query): the checks of a state
+map and its regions, the walk over the regions, the lines of an annotation file, the GPU handle and the protocol of the calls
+that list rows.  Host only apart from
 `device()`.
 
 len_vec rows: [n, start, stop, H, W, start_bin1, start_bin2, region_id, type (1 = diagonal), chrom].
@@ -79,6 +80,28 @@ def chrom_of(text):
     """the chromosome number of `chr<N>` or `<N>` in an annotation file (len_vec's column 9), None for any other name"""
     t = text[3:] if text.startswith("chr") else text
     return int(t) if t.isdigit() else None
+
+
+def is_number(text):
+    """a field of an annotation file that reads as an integer, with a sign at most"""
+    return text.lstrip("-").isdigit() and text.count("-") <= 1
+
+
+def annotation_lines(path):
+    """yields (line number from 1, the line, its fields) of a BED / BEDPE file, separated by tabs or spaces, without the
+    blank lines and those that start with #"""
+    with open(path) as fh:
+        for number, line in enumerate(fh, 1):
+            f = line.split()
+            if f and not f[0].startswith("#"):
+                yield number, line.rstrip("\n"), f
+
+
+def check_resolution(resolution):
+    res = int(resolution)
+    if res < 1:
+        raise ValueError("resolution must be >= 1")
+    return res
 
 
 def load_map(path, field="state_vec"):

@@ -22,6 +22,7 @@ import re
 import numpy as np
 
 from .maps import MAX_STATES, check_len_vec, check_state_vec, chrom_of, device, load_map, regions, stem
+from .maps import annotation_lines as _lines, check_resolution as _resolution, is_number as _number
 from .render import default_palette, load_palette, write_png
 
 LANES = 256                      # csrc/pileup.hip PILEUP_LANES: pile cells of a tile = lanes of a workgroup
@@ -121,10 +122,6 @@ def state_pileup(state_vec, len_vec, centres, flank, K=None, G=None):
 
 
 # ---- the anchor files -------------------------------------------------------------------------------------------------------
-def _number(text):
-    return text.lstrip("-").isdigit() and text.count("-") <= 1
-
-
 def _interval(path, number, start, stop):
     """-> the midpoint of [start, stop) in bp"""
     start, stop = int(start), int(stop)
@@ -141,21 +138,6 @@ def _group(path, number, names, name):
             raise ValueError("%s line %d: more than %d names (%s, then %r)" % (path, number, MAX_NAMES, ", ".join(names), name))
         names.append(name)
     return names.index(name)
-
-
-def _lines(path):
-    with open(path) as fh:
-        for number, line in enumerate(fh, 1):
-            f = line.split()
-            if f and not f[0].startswith("#"):
-                yield number, line.rstrip("\n"), f
-
-
-def _resolution(resolution):
-    res = int(resolution)
-    if res < 1:
-        raise ValueError("resolution must be >= 1")
-    return res
 
 
 def _anchors(rows, names, skipped):
