@@ -571,6 +571,34 @@ PHMRF_API int phmrf_pair_enrichment(const uint8_t* labels_dev, int H, int W, int
                                     int64_t* obs_host /* [2*C*C*K] */, int64_t* state_dist_host /* [D*K] */,
                                     int64_t* cat_dist_host /* [D*2*C*C] */, void* hip_stream);
 
+/* phmrf_pair_enrichment_null: ONE region against T circular shifts of its chromosome's annotation, the permutation null of
+ * phmrf_pair_enrichment (no block, no ABI bump).  The chromosome has B bins with the classes
+ * chrom_class[B] and optionally the segments chrom_seg[B]; the region's row bin i is the chromosome's bin row0 + i, its
+ * column bin j the bin col0 + j, dist0 = col0 - row0.  Under the shift s = shifts_host[t] (0 <= s < B) bin g carries
+ * chrom_class[(g + s) mod B] and chrom_seg[(g + s) mod B]; window, pair category p, "stored nodes count once" and the
+ * diagonal-block rule are phmrf_pair_enrichment's, whose row and column arrays are the slices at row0 and col0 of the shifted
+ * arrays.  Over the stored nodes inside the window:
+ *   obs_host    host int64 [T][P][K]: the nodes with category p under shift t and state k
+ *   expq_host   host int64 [T][P][K]: sum over d of cat_t[d][p] weight[d - d_lo][k], exactly, cat_t the cat_dist table of
+ *               phmrf_pair_enrichment under shift t; weight_host is u32 [D][K] with every entry <= 2^24, so expq is an
+ *               expectation in units of 2^-24 when the rows of weight are a distance's state shares in that fixed point
+ * obs does not depend on the weights.  [d_lo, d_lo + D) must hold the distances inside the window, as in
+ * phmrf_pair_enrichment; a window that holds no node gives zeros.  Nodes outside the window are never inspected.  Queued on
+ * hip_stream, returns when done.  Integers only: the same bytes from run to run.
+ * PHMRF_ERR_INVALID (nothing written) for a NULL pointer other than chrom_seg_dev_or_null, diagonal not 0 or 1, H < 1, W < 1,
+ * K < 1, C < 1, T < 1, D < 0, d_lo < 0, a diagonal block with H != W or row0 != col0, row0 < 0, col0 < 0, row0 + H > B,
+ * col0 + W > B, d_min < 0, d_max < d_min unless d_max is -1, a shift outside 0 .. B - 1, a weight above 2^24, a table range
+ * that does not hold every distance inside the window, a node inside the window whose label is >= K, or a class >= C met on a
+ * node inside the window under one of the call's shifts; PHMRF_ERR_UNSUPPORTED (nothing written) for K > 64, C > 8, T > 4096,
+ * T 2 C C K >= 2^26, B >= 2^31, n >= 2^31 - 64, |dist0| + H + W >= 2^31 or D max(K, 2 C C) >= 2^31. */
+PHMRF_API int phmrf_pair_enrichment_null(const uint8_t* labels_dev, int H, int W, int diagonal, int64_t row0, int64_t col0, int K,
+                                         int C, const uint8_t* chrom_class_dev /* [B] */,
+                                         const int32_t* chrom_seg_dev_or_null /* [B] */, int64_t B,
+                                         const int32_t* shifts_host /* [T] */, int T, int64_t d_min,
+                                         int64_t d_max /* -1: no upper limit */, int64_t d_lo, int64_t D,
+                                         const uint32_t* weight_host /* [D*K] */, int64_t* obs_host /* [T*2*C*C*K] */,
+                                         int64_t* expq_host /* [T*2*C*C*K] */, void* hip_stream);
+
 /* phmrf_state_pileup: the state map of ONE region piled up around a list of centres (no block, no ABI
  * bump).  The full matrix M is the H x W block itself, or for a diagonal block the symmetric matrix M[i][j] = the stored node
  * (min(i, j), max(i, j)), as in phmrf_render_states; labels in the node order of phmrf_smooth_labels.  A centre is

@@ -153,6 +153,12 @@ def parse_args(argv=None):
                       "limit); the default 0- is every distance")
     parser.add_option("--enrich_segments", default="0", help="--enrich: 1 = every line of --enrich_bed is a segment of its own "
                       "(a TAD list): bin pairs inside one interval are counted apart from pairs across intervals")
+    parser.add_option("--enrich_null", default="0", help="--enrich: 0 = off; N in 1 .. 10000 = a permutation null of N draws, every "
+                      "draw a random circular shift of the annotation along every chromosome, recounted on the GPU with its "
+                      "own distance-matched expectation; adds the null's tables, z-scores and p-values to enrich_<stem>.npz and "
+                      "writes enrich_<stem>_null.txt")
+    parser.add_option("--enrich_null_min", default="1000000", help="--enrich_null: the smallest shift in bp (at least one bin)")
+    parser.add_option("--enrich_null_seed", default="0", help="--enrich_null: the seed of the shifts")
     parser.add_option("--pileup", default="", help="skip loading data and fitting: pile the states of this .mat up around the "
                       "anchors of --pileup_bed or the anchor pairs of --pileup_bedpe (the state counts per cell of a window of "
                       "+- --pileup_flank around every anchor, summed over the anchors of a name); writes pileup_<stem>.npz, "
@@ -455,6 +461,26 @@ def check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments,
     return wins[0]
 
 
+def check_enrich_null(enrich, enrich_null="0", enrich_null_min="1000000", enrich_null_seed="0", resolution="50000"):
+    """--enrich_null N, --enrich_null_min BP and --enrich_null_seed S go with --enrich -> (N, the smallest shift in bins, the
+    seed); N = 0: no null.  (N 2 C C K < 2^26 is checked once the map and the annotation are read: enrich.check_null_size.)"""
+    try:
+        n, min_bp, seed = int(enrich_null), int(enrich_null_min), int(enrich_null_seed)
+    except ValueError:
+        raise SystemExit("--enrich_null, --enrich_null_min and --enrich_null_seed must be integers")
+    if not enrich:
+        if (n, min_bp, seed) != (0, 1000000, 0):
+            raise SystemExit("--enrich_null, --enrich_null_min and --enrich_null_seed go with --enrich")
+        return 0, 0, 0
+    if not 0 <= n <= 10000:
+        raise SystemExit("--enrich_null must be 0 (no null) or lie in 1 .. 10000, not %d" % n)
+    if n == 0 and (min_bp, seed) != (1000000, 0):
+        raise SystemExit("--enrich_null_min and --enrich_null_seed go with --enrich_null N")
+    if min_bp < 0 or seed < 0:
+        raise SystemExit("--enrich_null_min and --enrich_null_seed must be >= 0")
+    return n, max(1, min_bp // int(resolution)), seed
+
+
 def check_pileup(pileup, pileup_bed, pileup_bedpe, pileup_field, pileup_flank, pileup_shift, resolution, segment, postprocess,
                  compare, domains, render, tracks, enrich, ancestral, save_model, profile, filter_device, consensus="", query=""):
     """--pileup FILE.mat with --pileup_bed FILE or --pileup_bedpe FILE reads one finished state map and a list of anchors: it
@@ -551,7 +577,8 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
         tracks_dist="0-", enrich="", enrich_bed="", enrich_field="state_vec", enrich_dist="0-", enrich_segments="0",
         pileup="", pileup_bed="", pileup_bedpe="", pileup_field="state_vec", pileup_flank="1000000", pileup_shift="0",
         pileup_colors="", consensus="", consensus_field="state_vec", consensus_match="0", consensus_support="-1",
-        consensus_area="-1", query="", query_bed="", query_bedpe="", query_field="state_vec", query_shift="0"):
+        consensus_area="-1", query="", query_bed="", query_bedpe="", query_field="state_vec", query_shift="0",
+        enrich_null="0", enrich_null_min="1000000", enrich_null_seed="0"):
     check_query(query, query_bed, query_bedpe, query_field, query_shift, resolution, segment, postprocess,
                 compare or compare_with, domains, render, tracks, enrich, pileup, consensus, ancestral, save_model, profile,
                 filter_device)
@@ -564,6 +591,7 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
     check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments, resolution, segment, postprocess,
                  compare or compare_with, domains, render, tracks, ancestral, save_model, profile, filter_device,
                  consensus=consensus, query=query)
+    null = check_enrich_null(enrich, enrich_null, enrich_null_min, enrich_null_seed, resolution)
     check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment, postprocess, compare or compare_with, domains,
                  ancestral, save_model, profile, filter_device, consensus=consensus, query=query)
     side = check_render(render, render_field, render_side, render_outline, render_conf, segment, postprocess,
@@ -600,9 +628,13 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
         print("pile-up written: %s" % out)
         return out
     if enrich:
-        from phylo_hmrf_amd.enrich import enrich_files
-        out = enrich_files(enrich, enrich_bed, str(output_path), int(resolution), field=enrich_field, window_bp=enrich_dist,
-                           segments=str(enrich_segments) == "1")
+        from phylo_hmrf_amd.enrich import NullSizeError, enrich_files
+        try:
+            out = enrich_files(enrich, enrich_bed, str(output_path), int(resolution), field=enrich_field, window_bp=enrich_dist,
+                               segments=str(enrich_segments) == "1", null=null[0], null_min_bp=int(enrich_null_min),
+                               null_seed=null[2])
+        except NullSizeError as e:
+            raise SystemExit("--enrich_null: %s" % e)
         print("enrichment written: %s" % out)
         return out
     if tracks:
@@ -820,4 +852,5 @@ if __name__ == "__main__":
         pileup_colors=opts.pileup_colors, consensus=opts.consensus, consensus_field=opts.consensus_field,
         consensus_match=opts.consensus_match, consensus_support=opts.consensus_support, consensus_area=opts.consensus_area,
         query=opts.query, query_bed=opts.query_bed, query_bedpe=opts.query_bedpe, query_field=opts.query_field,
-        query_shift=opts.query_shift)
+        query_shift=opts.query_shift, enrich_null=opts.enrich_null, enrich_null_min=opts.enrich_null_min,
+        enrich_null_seed=opts.enrich_null_seed)

@@ -121,6 +121,8 @@ SIGNATURES = {
     "phmrf_render_states": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp],
     "phmrf_state_tracks": [_vp, _i, _i, _i, _i64, _i, _i64, _i64, _lp, _lp, _vp],
     "phmrf_pair_enrichment": [_vp, _i, _i, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _lp, _lp, _lp, _vp],
+    "phmrf_pair_enrichment_null": [_vp, _i, _i, _i, _i64, _i64, _i, _i, _vp, _vp, _i64, _ip, _i, _i64, _i64, _i64, _i64,
+                                   ctypes.POINTER(ctypes.c_uint32), _lp, _lp, _vp],
     "phmrf_state_pileup": [_vp, _i, _i, _i, _i, _i, _i, _lp, _vp, _vp, _vp, _lp, _vp],
     "phmrf_rect_states": [_vp, _vp, _i, _i, _i, _i, _i64, _ip, _ip, ctypes.POINTER(ctypes.c_uint8), _i64, _lp, _lp, _vp],
     "phmrf_state_hist": [_vp, _i, _i, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)],
