@@ -318,6 +318,28 @@ PHMRF_API int phmrf_mrf_coarse_pass(phmrf_block_t b, double beta, int scale, int
  * lam_out[nc,4] = weights of its forward pairs (E, SW, S, SE; without beta).  Outputs may be NULL. */
 PHMRF_API int phmrf_block_coarse_problem(phmrf_block_t b, double beta, int scale, int offset, int alpha, int64_t* nc,
                                          float* D_out, float* lam_out);
+/* The coarse problems of up to four labels built in ONE pass, as a solve's coarse sweep builds a batch (tests): nl in 1..4
+ * labels alphas[nl]; D_out[nl, nc] and lam_out[nl, nc, 4] as in phmrf_block_coarse_problem.  Outputs may be NULL. */
+PHMRF_API int phmrf_block_coarse_problems(phmrf_block_t b, double beta, int scale, int offset, const int* alphas, int nl,
+                                          int64_t* nc, float* D_out, float* lam_out);
+/* The coarse alpha-expansions of every label named by the bits of label_mask at one scale and offset, ascending, in batches
+ * of four, exactly as a round of phmrf_mrf_solve runs them (one pass builds a batch's problems; a label whose predecessors
+ * in the batch moved something gets its problem rebuilt first).  *changed: nodes changed in all; changed_label[K] (may be
+ * NULL): per label.  stamps != 0: the sweep runs as inside a solve -- change stamps zeroed, launch tick 1 on entry, so the
+ * rebuild is gated per wavefront and the apply passes stamp; the solve-scope state is left as the end of a solve leaves
+ * it.  stamps == 0: no stamps, a rebuild covers the whole block.  PHMRF_ERR_STATE while a solve is in progress. */
+PHMRF_API int phmrf_mrf_coarse_sweep(phmrf_block_t b, double beta, int scale, int offset, uint64_t label_mask, int shift_r,
+                                     int shift_c, int stamps, int64_t* changed, int64_t* changed_label);
+/* The child problem of the coarse-to-fine start (phmrf_solve_opts.coarse_start; tests): the block of 4 x 4 super-cells,
+ * *Hc x *Wc with *nc nodes; nbr_out[nc, 8] / wgt_out[nc, 8]: its adjacency rows (neighbours in the order NW N NE W E SW S
+ * SE, compacted, -1 / 0 padded; weights = sums over the crossing edges); logprob_out[nc, K]: sums over each super-cell.
+ * Outputs may be NULL.  PHMRF_ERR_STATE where a cold solve would not start coarse-to-fine: no complete 8-neighbour grid,
+ * a row tile, n < 1024, H or W < 8. */
+PHMRF_API int phmrf_block_c2f_problem(phmrf_block_t b, int* Hc, int* Wc, int64_t* nc, int32_t* nbr_out, float* wgt_out,
+                                      float* logprob_out);
+/* labels of the block = labels_c[super-cell of the node] (labels_c[nc], the child of phmrf_block_c2f_problem; same
+ * conditions). */
+PHMRF_API int phmrf_block_c2f_prolong(phmrf_block_t b, const int32_t* labels_c, int64_t nc);
 PHMRF_API int phmrf_mrf_energy(phmrf_block_t b, double beta, double* e_total, double* e_unary, double* e_pair);
 
 /* ---- b3: posteriors, costs, sufficient statistics ------------------------------------------- */

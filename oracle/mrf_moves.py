@@ -365,6 +365,8 @@ def strip_fusion(g, unary, labels, prop, beta, H, W, diagonal, orient, shift_r, 
 
     def wlook(a, b):
         q = np.where((a >= 0) & (b >= 0), a * n + b, -1)
+        if len(keys) == 0:                              # (a graph without edges: a coarse problem whose pairs all weigh 0)
+            return np.zeros(q.shape)
         p = np.clip(np.searchsorted(keys, q.ravel()), 0, len(keys) - 1)
         hit = keys[p] == q.ravel()
         return np.where(hit, g.wgt[p], 0.0).reshape(q.shape)
@@ -511,6 +513,40 @@ def coarse_cross_weight(g, H, W, diagonal, s, off):
     return np.bincount(cnode[a][x], weights=g.w[x], minlength=nc) + np.bincount(cnode[b][x], weights=g.w[x], minlength=nc)
 
 
+def coarse_solve_apply(D, lam, cnode, Hc, Wc, labels, beta, diagonal, alpha, shift_r=0, shift_c=0):
+    """The second half of a coarse alpha-expansion: the super-cell problem (D, lam) solved by one strip pass per orientation
+    (strip_fusion on the coarse grid, all super-cells start at 'keep'), then applied to `labels` -- whatever labelling the
+    problem was built from.  In place; returns the number of changed nodes."""
+    nc = D.shape[0]
+    ci, cj = grid_coords(Hc, Wc, diagonal)
+    if diagonal:
+        idmap = -np.ones((Hc, Wc), dtype=np.int64)
+        idmap[ci, cj] = np.arange(nc)
+    else:
+        idmap = np.arange(nc).reshape(Hc, Wc)
+    e, w = [], []
+    for q, (di, dj) in enumerate(((0, 1), (1, -1), (1, 0), (1, 1))):
+        i2, j2 = ci + di, cj + dj
+        ok = (i2 < Hc) & (j2 >= 0) & (j2 < Wc)
+        ok[ok] &= idmap[i2[ok], j2[ok]] >= 0
+        src = np.flatnonzero(ok)
+        e.append(np.stack([src, idmap[i2[src], j2[src]]], 1))
+        w.append(lam[src, q])
+    e, w = np.concatenate(e), np.concatenate(w)
+    keep = w != 0
+    gc = Graph(nc, e[keep], w[keep])
+    uc = np.stack([np.zeros(nc), D], 1)
+    xl = np.zeros(nc, dtype=np.int64)
+    strip_fusion(gc, uc, xl, np.ones(nc, dtype=np.int64), beta, Hc, Wc, diagonal, 0, shift_r % 6, shift_c % 64)
+    strip_fusion(gc, uc, xl, np.ones(nc, dtype=np.int64), beta, Hc, Wc, diagonal, 1, (shift_r + 3) % 6, (shift_c + 31) % 64)
+    lab = np.asarray(labels)
+    sel = (xl[cnode] == 1) & (lab != alpha)
+    labels[sel] = alpha
+    return int(sel.sum())
+
+
+# (coarse_expansion = coarse_problem, then the lines of coarse_solve_apply above: keep the two in step --
+#  tests/test_coarse_reference_cpu.py holds them together)
 def coarse_expansion(g, unary, labels, beta, H, W, diagonal, s, off, alpha, shift_r=0, shift_c=0):
     """One coarse alpha-expansion: the super-cell problem solved by one strip pass per orientation (strip_fusion on the
     coarse grid, all super-cells start at 'keep'), then applied.  In place; returns the number of changed nodes."""
@@ -541,3 +577,51 @@ def coarse_expansion(g, unary, labels, beta, H, W, diagonal, s, off, alpha, shif
     sel = (xl[cnode] == 1) & (lab != alpha)
     labels[sel] = alpha
     return int(sel.sum())
+
+
+COARSE_WAVE = 64     # thread columns (j + off) of one wavefront of the coarsen pass (coarse.hip)
+
+
+def coarse_sweep(g, unary, labels, beta, H, W, diagonal, s, off, alphas, sr, sc, batch=4, stale=False):
+    """The coarse alpha-expansions of `alphas`, in that order, at one scale and offset (model of solve.hip's coarse sweep).  In
+    place; returns the changed count per label (a list in the order of `alphas`).
+
+    stale=False: the one-by-one sequence, each label's problem built from the labelling its predecessors left -- what the
+    kernels must reproduce, in whatever batches they build.
+    The other values are WRONG answers, for the preconditions of tests (a case in which they give the right labelling
+    cannot tell a broken shortcut from a working one):
+    stale=True: every problem of a batch of `batch` labels is built from the labelling at the batch's start and never rebuilt.
+    stale="waves": a label whose predecessors in the batch moved something rebuilds, but only the super-cells of the
+    wavefronts -- COARSE_WAVE thread columns j + off of the s grid rows of one coarse row -- that hold a node which changed since the
+    batch's start; the rest keep the numbers of the batch's start.  The kernel marks a changed node AND its neighbours
+    (stale="waves-dilated": equal to the one-by-one sequence, since a super-cell's numbers depend on its nodes and their
+    neighbours only); "waves" leaves the neighbours out."""
+    assert stale in (False, True, "waves", "waves-dilated")
+    ii, jj = grid_coords(H, W, diagonal)
+    out = []
+    for t0 in range(0, len(alphas), batch):
+        group = list(alphas[t0:t0 + batch])
+        if stale is False:
+            for a in group:
+                out.append(coarse_expansion(g, unary, labels, beta, H, W, diagonal, s, off, a, sr, sc))
+            continue
+        start = np.asarray(labels).copy()
+        probs = [coarse_problem(g, unary, start, beta, H, W, diagonal, s, off, a) for a in group]
+        for q, a in enumerate(group):
+            D, lam, cnode, Hc, Wc = probs[q]
+            moved = np.asarray(labels) != start
+            if stale is not True and q > 0 and moved.any():
+                if stale == "waves-dilated":
+                    touched = moved.copy()
+                    touched[g.col[moved[g.src]]] = True
+                else:
+                    touched = moved
+                Wv = (Wc * s + COARSE_WAVE - 1) // COARSE_WAVE
+                dirty = np.zeros((Hc, Wv), dtype=bool)
+                dirty[(ii[touched] + off) // s, (jj[touched] + off) // COARSE_WAVE] = True
+                D2, lam2 = coarse_problem(g, unary, labels, beta, H, W, diagonal, s, off, a)[:2]
+                ci, cj = grid_coords(Hc, Wc, diagonal)
+                redo = dirty[ci, (cj * s) // COARSE_WAVE]
+                D, lam = np.where(redo, D2, D), np.where(redo[:, None], lam2, lam)
+            out.append(coarse_solve_apply(D, lam, cnode, Hc, Wc, labels, beta, diagonal, a, sr, sc))
+    return out

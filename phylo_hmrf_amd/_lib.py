@@ -108,6 +108,10 @@ SIGNATURES = {
     "phmrf_mrf_energy": [_vp, _d, _dp, _dp, _dp],
     "phmrf_mrf_coarse_pass": [_vp, _d, _i, _i, _i, _i, _i, _lp],
     "phmrf_block_coarse_problem": [_vp, _d, _i, _i, _i, _lp, _fp, _fp],
+    "phmrf_block_coarse_problems": [_vp, _d, _i, _i, ctypes.POINTER(_i), _i, _lp, _fp, _fp],
+    "phmrf_mrf_coarse_sweep": [_vp, _d, _i, _i, ctypes.c_uint64, _i, _i, _i, _lp, _lp],
+    "phmrf_block_c2f_problem": [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), _lp, _ip, _fp, _fp],
+    "phmrf_block_c2f_prolong": [_vp, _ip, _i64],
     "phmrf_posterior_stats": [_vp, _d, _i, _dp, _dp, _dp],
     "phmrf_posterior_stats_dev": [_vp, _d, _i, _vp],
     "phmrf_posterior_summary": [_vp, _d, _i, _fp, ctypes.POINTER(ctypes.c_uint8), _fp],

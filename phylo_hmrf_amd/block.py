@@ -298,6 +298,50 @@ class Block(object):
                                                  D.ctypes.data_as(fp), lam.ctypes.data_as(fp)))
         return D, lam
 
+    def coarse_problems(self, beta, scale, offset, alphas):
+        """the problems of up to four labels built in one pass, as a coarse sweep builds a batch -> (D[nl, nc], lam[nl, nc, 4])
+        (tests)."""
+        al = (ctypes.c_int * len(alphas))(*[int(a) for a in alphas])
+        nc = ctypes.c_int64(0)
+        check(self._L.phmrf_block_coarse_problems(self._h, float(beta), int(scale), int(offset), al, len(alphas),
+                                                  ctypes.byref(nc), None, None))
+        D = np.zeros((len(alphas), nc.value), dtype=np.float32)
+        lam = np.zeros((len(alphas), nc.value, 4), dtype=np.float32)
+        fp = ctypes.POINTER(ctypes.c_float)
+        check(self._L.phmrf_block_coarse_problems(self._h, float(beta), int(scale), int(offset), al, len(alphas),
+                                                  ctypes.byref(nc), D.ctypes.data_as(fp), lam.ctypes.data_as(fp)))
+        return D, lam
+
+    def coarse_sweep(self, beta, scale, offset, labels=None, shift_r=0, shift_c=0, stamps=False):
+        """the coarse alpha-expansions of `labels` (default: all K) at one scale and offset, ascending, in batches of four as a
+        solve's round runs them; stamps: with the change stamps of a solve -> (changed in all, changed per label int64[K])"""
+        mask = 0
+        for a in (range(self.K) if labels is None else labels):
+            mask |= 1 << int(a)
+        c = ctypes.c_int64(0)
+        per = np.zeros(self.K, dtype=np.int64)
+        check(self._L.phmrf_mrf_coarse_sweep(self._h, float(beta), int(scale), int(offset), ctypes.c_uint64(mask), int(shift_r),
+                                             int(shift_c), int(bool(stamps)), ctypes.byref(c), ptr_i64(per)))
+        return c.value, per
+
+    def c2f_problem(self):
+        """the child problem of the coarse-to-fine start -> (Hc, Wc, nbr int32[nc, 8], wgt float32[nc, 8], logprob float32[nc, K])
+        (tests)."""
+        Hc, Wc, nc = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+        check(self._L.phmrf_block_c2f_problem(self._h, ctypes.byref(Hc), ctypes.byref(Wc), ctypes.byref(nc), None, None, None))
+        nbr = np.empty((nc.value, 8), dtype=np.int32)
+        wgt = np.empty((nc.value, 8), dtype=np.float32)
+        lp = np.empty((nc.value, self.K), dtype=np.float32)
+        fp = ctypes.POINTER(ctypes.c_float)
+        check(self._L.phmrf_block_c2f_problem(self._h, ctypes.byref(Hc), ctypes.byref(Wc), ctypes.byref(nc), ptr_i32(nbr),
+                                              wgt.ctypes.data_as(fp), lp.ctypes.data_as(fp)))
+        return Hc.value, Wc.value, nbr, wgt, lp
+
+    def c2f_prolong(self, labels_c):
+        """labels of the block = labels_c[4 x 4 super-cell of the node] (tests)."""
+        lab = np.ascontiguousarray(np.asarray(labels_c), dtype=np.int32)
+        check(self._L.phmrf_block_c2f_prolong(self._h, ptr_i32(lab), lab.shape[0]))
+
     def energy(self, beta):
         e, eu, ep = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0)
         check(self._L.phmrf_mrf_energy(self._h, float(beta), ctypes.byref(e), ctypes.byref(eu), ctypes.byref(ep)))

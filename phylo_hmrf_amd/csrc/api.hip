@@ -1244,6 +1244,113 @@ int phmrf_block_coarse_problem(phmrf_block_t b, double beta, int scale, int offs
   return PHMRF_OK;
 }
 
+int phmrf_block_coarse_problems(phmrf_block_t b, double beta, int scale, int offset, const int* alphas, int nl, int64_t* nc,
+                                float* D_out, float* lam_out) {
+  PHMRF_TRY(check_solvable(b));
+  PHMRF_CHECK(nc && alphas, PHMRF_ERR_INVALID, "NULL argument");
+  PHMRF_CHECK(b->has_grid, PHMRF_ERR_STATE, "coarse moves need phmrf_block_set_grid");
+  PHMRF_CHECK(scale == 2 || scale == 4 || scale == 8, PHMRF_ERR_INVALID, "scale must be 2, 4 or 8");
+  PHMRF_CHECK(offset >= 0 && offset < scale, PHMRF_ERR_INVALID, "offset must be in [0, scale)");
+  PHMRF_CHECK(nl >= 1 && nl <= 4, PHMRF_ERR_INVALID, "nl must be in [1, 4]");
+  for (int q = 0; q < nl; ++q) PHMRF_CHECK(alphas[q] >= 0 && alphas[q] < b->K, PHMRF_ERR_INVALID, "alpha must be in [0, K)");
+  *nc = coarse_nodes(b, scale, offset);
+  if (!D_out && !lam_out) return PHMRF_OK;
+  const int level = scale == 2 ? 0 : (scale == 4 ? 1 : 2);
+  phmrf_block* ch[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (int q = 0; q < nl; ++q) PHMRF_TRY(coarse_child(b, 4 * level + q, &ch[q]));
+  if (!b->uT_valid) PHMRF_TRY(launch_unary_planes(b));
+  PHMRF_TRY(launch_coarsen_batch(b, ch, alphas, nl, scale, offset, (float)beta, nullptr, -1, false));
+  for (int q = 0; q < nl; ++q) {
+    if (D_out) PHMRF_TRY(download(D_out + (size_t)q * *nc, ch[q]->uT + *nc, (size_t)*nc * sizeof(float), b->stream));
+    if (lam_out) PHMRF_TRY(download(lam_out + (size_t)q * *nc * 4, ch[q]->fwd_w, (size_t)*nc * sizeof(float4), b->stream));
+  }
+  return PHMRF_OK;
+}
+
+int phmrf_mrf_coarse_sweep(phmrf_block_t b, double beta, int scale, int offset, uint64_t label_mask, int shift_r, int shift_c,
+                           int stamps, int64_t* changed, int64_t* changed_label) {
+  PHMRF_TRY(check_solvable(b));
+  PHMRF_CHECK(!b->ss, PHMRF_ERR_STATE, "a solve is in progress");
+  PHMRF_CHECK(b->has_grid, PHMRF_ERR_STATE, "coarse moves need phmrf_block_set_grid");
+  PHMRF_CHECK(b->has_labels, PHMRF_ERR_STATE, "labels not set");
+  PHMRF_CHECK(scale == 2 || scale == 4 || scale == 8, PHMRF_ERR_INVALID, "scale must be 2, 4 or 8");
+  PHMRF_CHECK(offset >= 0 && offset < scale, PHMRF_ERR_INVALID, "offset must be in [0, scale)");
+  PHMRF_CHECK(shift_r >= 0 && shift_r <= 5 && shift_c >= 0 && shift_c <= 63, PHMRF_ERR_INVALID, "shift out of range");
+  PHMRF_CHECK(b->K >= 64 || (label_mask >> b->K) == 0, PHMRF_ERR_INVALID, "label_mask names a label >= K");
+  b->labels_are_slot = 0;
+  const int level = scale == 2 ? 0 : (scale == 4 ? 1 : 2);
+  const size_t lab_bytes = (size_t)N_COARSE * MAX_LABELS * sizeof(unsigned long long);
+  if (!b->coarse_lab) {
+    PHMRF_TRY(dev_alloc(&b->coarse_lab, (size_t)N_COARSE * MAX_LABELS));
+    PHMRF_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->coarse_lab_host), lab_bytes));
+  }
+  PHMRF_HIP(hipMemsetAsync(b->coarse_lab, 0, lab_bytes, b->stream));
+  PHMRF_TRY(zero_counter(b));
+  if (stamps) {         // as solve_begin leaves them: no node stamped, the first launch tick
+    if (!b->stamp) PHMRF_TRY(dev_alloc(&b->stamp, (size_t)b->n));
+    PHMRF_HIP(hipMemsetAsync(b->stamp, 0, (size_t)b->n * sizeof(uint16_t), b->stream));
+    b->tick = 1;
+  }
+  int st = coarse_sweep_nocount(b, (float)beta, level, offset, shift_r, shift_c, 0, b->K, label_mask);
+  if (st == PHMRF_OK && hipMemcpyAsync(b->coarse_lab_host, b->coarse_lab, lab_bytes, hipMemcpyDeviceToHost, b->stream) != hipSuccess)
+    st = PHMRF_ERR_HIP;
+  const int st_read = read_counter(b, changed);
+  if (stamps) solve_scope_exit(b);
+  PHMRF_TRY(st);
+  PHMRF_TRY(st_read);
+  if (changed_label)
+    for (int a = 0; a < b->K; ++a) changed_label[a] = (int64_t)b->coarse_lab_host[(size_t)level * MAX_LABELS + a];
+  return PHMRF_OK;
+}
+
+// ---- the coarse-to-fine start's child problem (c2f.hip; built by solve.hip) ----------------------------------------------
+static int c2f_ready(phmrf_block_t b) {
+  PHMRF_CHECK(b, PHMRF_ERR_INVALID, "block is NULL");
+  PHMRF_CHECK(!b->ss, PHMRF_ERR_STATE, "a solve is in progress");
+  PHMRF_CHECK(c2f_applies(b), PHMRF_ERR_STATE,
+              "the coarse-to-fine start needs a complete 8-neighbour grid block (no row tile) with n >= 1024 and H, W >= 8");
+  return c2f_child(b);
+}
+
+int phmrf_block_c2f_problem(phmrf_block_t b, int* Hc, int* Wc, int64_t* nc, int32_t* nbr_out, float* wgt_out, float* logprob_out) {
+  PHMRF_TRY(check_solvable(b));
+  PHMRF_CHECK(Hc && Wc && nc, PHMRF_ERR_INVALID, "NULL argument");
+  PHMRF_TRY(c2f_ready(b));
+  phmrf_block* c = b->c2f;
+  *Hc = b->c2f_Hc;
+  *Wc = b->c2f_Wc;
+  *nc = c->n;
+  if (nbr_out) PHMRF_TRY(download(nbr_out, c->nbr, (size_t)c->n * 8 * sizeof(int32_t), b->stream));
+  if (wgt_out) PHMRF_TRY(download(wgt_out, c->wgt, (size_t)c->n * 8 * sizeof(float), b->stream));
+  if (logprob_out) {
+    PHMRF_TRY(launch_c2f_logprob(b, c, b->c2f_Wc, C2F_SCALE));
+    c->has_logprob = true;
+    c->uT_valid = false;
+    PHMRF_TRY(download(logprob_out, c->logprob, (size_t)c->n * b->K * sizeof(float), b->stream));
+  }
+  return PHMRF_OK;
+}
+
+int phmrf_block_c2f_prolong(phmrf_block_t b, const int32_t* labels_c, int64_t nc) {
+  PHMRF_CHECK(b && labels_c, PHMRF_ERR_INVALID, "NULL argument");
+  PHMRF_TRY(c2f_ready(b));
+  phmrf_block* c = b->c2f;
+  PHMRF_CHECK(nc == c->n, PHMRF_ERR_INVALID, "nc is not the number of 4 x 4 super-cells");
+  std::vector<uint8_t> tmp((size_t)nc);
+  for (int64_t i = 0; i < nc; ++i) {
+    PHMRF_CHECK(labels_c[i] >= 0 && labels_c[i] < b->K, PHMRF_ERR_INVALID, "label out of range [0,K)");
+    tmp[(size_t)i] = (uint8_t)labels_c[i];
+  }
+  PHMRF_TRY(upload(c->labels, tmp.data(), (size_t)nc, b->stream));
+  c->has_labels = true;
+  c->labels_are_slot = 0;
+  PHMRF_TRY(launch_c2f_prolong(b, c, b->c2f_Wc, C2F_SCALE));
+  PHMRF_HIP(hipStreamSynchronize(b->stream));
+  b->has_labels = true;
+  b->labels_are_slot = 0;
+  return PHMRF_OK;
+}
+
 // ---- row tiles (tile.hip) -----------------------------------------------------------------------
 
 int phmrf_block_set_tile(phmrf_block_t b, int top, int bottom, int64_t sched_n) {

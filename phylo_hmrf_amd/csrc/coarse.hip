@@ -58,7 +58,11 @@ __device__ __forceinline__ float comp4(const float4& v, int e) { return e == 0 ?
 // the neighbours' labels -- two thirds of the kernel's time, and the same for every label -- are read once for up to four
 // labels; each label's problem goes to a child block of its own.  Per label the arithmetic is what the one-label pass
 // does, in the same order, so a problem built in a batch and one rebuilt alone (`rebuild`: only when a move since the
-// batch has changed the labelling, coarse_apply_kernel's flag) are the same numbers.
+// batch has changed the labelling, coarse_apply_kernel's flag) are the same numbers.  The same ROUNDINGS, too: every
+// beta-weighted term enters D through an explicit fused multiply-add.  Written as D += beta * dt the compiler fused it in
+// the one-label form and, in the batched forms, shared the rounded product beta * dG between the labels -- with a beta or
+// weights that are no dyadic rationals the batch's D and the rebuild's then differed in the last bits, and a rebuild that
+// is gated per wavefront left a problem mixed from both (tests/test_gpu_coarse_sweep.py, test_batched_build_real_valued).
 struct CoarseOut {
   float* c_uT[4];
   float4* c_fwd[4];
@@ -149,12 +153,12 @@ __device__ __forceinline__ void coarsen_row(const CoarseGeom& g, int I, int64_t 
       for (int q = 0; q < NL; ++q) {
         const int alpha = out.alpha[q];
         if (inside) {
-          D[q] -= beta * t00;
+          D[q] = __fmaf_rn(-beta, t00, D[q]);
         } else {
           const bool mine = li == alpha, other = lj == alpha;
           const float lv = (mine || other) ? 0.f : lvG;
           const float dt = mine ? 0.f : (other ? -w : dG);
-          D[q] += beta * dt;
+          D[q] = __fmaf_rn(beta, dt, D[q]);
           if (dI == 0 && dJ == 1) lam[q][0] += lv;
           else if (dI == 1) lam[q][2 + dJ] += lv;           // SW (dJ -1) -> 1, S -> 2, SE -> 3
           // (dI == 0, dJ == -1): the pair's slot is the E slot of the other super-cell, which adds it below
@@ -176,7 +180,7 @@ __device__ __forceinline__ void coarsen_row(const CoarseGeom& g, int I, int64_t 
         const bool mine = li == alpha, other = lj == alpha;
         const float lv = (mine || other) ? 0.f : lvG;
         const float dt = mine ? 0.f : (other ? -w : dG);
-        D[q] += beta * dt;
+        D[q] = __fmaf_rn(beta, dt, D[q]);
         if (dI == 0 && dJ == 1) lam[q][0] += lv;            // the holder sits in my E neighbour (a fine SW edge)
       }
     }
@@ -201,7 +205,7 @@ __device__ __forceinline__ void coarsen_row(const CoarseGeom& g, int I, int64_t 
     // A super-cell whose switch cost exceeds everything its pairs could give back (lambda <= w on every cross edge) is in
     // no optimal switch set: taking it out of any set lowers the energy.  It is pinned (strip.hip: unary >= 1e29 = no
     // proposal), and a strip of pinned super-cells costs the strip kernel one look at the unary plane.
-    out.c_uT[q][nc + c] = (D[q] > beta * wcross * 1.0001f + 1e-6f) ? 1.0e30f : D[q];
+    out.c_uT[q][nc + c] = (D[q] > __fmaf_rn(beta * wcross, 1.0001f, 1e-6f)) ? 1.0e30f : D[q];
     out.c_fwd[q][c] = make_float4(lam[q][0], lam[q][1], lam[q][2], lam[q][3]);
     out.c_labels[q][c] = 0;
   }

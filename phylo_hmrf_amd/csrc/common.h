@@ -329,6 +329,9 @@ void coarse_children_destroy(phmrf_block* b);
 int coarse_sweep_nocount(phmrf_block* b, float beta, int level, int off, int shift_r, int shift_c, int alpha_lo, int alpha_hi,
                          unsigned long long label_mask = ~0ull);
 int tile_queue_boundary(phmrf_block* b);
+bool c2f_applies(const phmrf_block* b);                 // the block qualifies for the coarse-to-fine start (c2f.hip)
+int c2f_child(phmrf_block* b);                          // -> b->c2f, the block of its 4 x 4 super-cells (built once)
+void solve_scope_exit(phmrf_block* b);
 
 inline int tile_threads(int K) { return K <= 40 ? 256 : 128; }
 inline int padded_k(int K) { return (K % 2 == 0) ? K + 1 : K; }  // odd LDS row stride: conflict-free row-per-lane access

@@ -262,15 +262,15 @@ struct EndSolves {
   }
 };
 
-// The coarse-to-fine start of a cold solve (c2f.hip): the labelling problem of the block's 4 x 4 super-cells as a block of
-// its own (created at the first cold solve; its graph is built once, the graph of the block being constant over a fit),
-// solved from ITS cold start by this same solver -- which recurses while the coarse block is large --, and copied down.
-// *started: the block's labels are the prolongated coarse labels (otherwise the caller takes argmax_k logprob).
-static int c2f_start(phmrf_block* b, double beta, const phmrf_solve_opts& o, bool* started) {
-  *started = false;
-  if (o.coarse_start <= 0 || !b->has_grid || !b->fwd_w || b->num_neighbor != 8 || !b->grid_complete) return PHMRF_OK;
-  if (is_tile(b) || !o.use_strips) return PHMRF_OK;
-  if (b->n < 1024 || b->H < 2 * C2F_SCALE || b->W < 2 * C2F_SCALE) return PHMRF_OK;
+namespace phmrf {
+// (the blocks that start coarse-to-fine: a complete 8-neighbour grid that is no row tile and large enough for a coarse grid)
+bool c2f_applies(const phmrf_block* b) {
+  if (!b->has_grid || !b->fwd_w || b->num_neighbor != 8 || !b->grid_complete || is_tile(b)) return false;
+  return b->n >= 1024 && b->H >= 2 * C2F_SCALE && b->W >= 2 * C2F_SCALE;
+}
+
+// the child block of the coarse-to-fine start, b->c2f, with its graph and grid tables: built at the first call
+int c2f_child(phmrf_block* b) {
   const int s = C2F_SCALE;
   if (!b->c2f) {
     const int Hc = (b->H + s - 1) / s, Wc = (b->W + s - 1) / s;
@@ -302,8 +302,21 @@ static int c2f_start(phmrf_block* b, double beta, const phmrf_solve_opts& o, boo
     b->c2f_Hc = Hc;
     b->c2f_Wc = Wc;
   }
+  b->c2f->stream = b->stream;
+  return PHMRF_OK;
+}
+}  // namespace phmrf
+
+// The coarse-to-fine start of a cold solve (c2f.hip): the labelling problem of the block's 4 x 4 super-cells as a block of
+// its own (created at the first cold solve; its graph is built once, the graph of the block being constant over a fit),
+// solved from ITS cold start by this same solver -- which recurses while the coarse block is large --, and copied down.
+// *started: the block's labels are the prolongated coarse labels (otherwise the caller takes argmax_k logprob).
+static int c2f_start(phmrf_block* b, double beta, const phmrf_solve_opts& o, bool* started) {
+  *started = false;
+  if (o.coarse_start <= 0 || !o.use_strips || !c2f_applies(b)) return PHMRF_OK;
+  const int s = C2F_SCALE;
+  PHMRF_TRY(c2f_child(b));
   phmrf_block* c = b->c2f;
-  c->stream = b->stream;
   PHMRF_TRY(launch_c2f_logprob(b, c, b->c2f_Wc, s));
   c->has_logprob = true;
   c->uT_valid = false;
