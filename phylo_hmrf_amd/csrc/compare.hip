@@ -52,12 +52,7 @@ __global__ __launch_bounds__(256) void contingency_kernel(const uint8_t* __restr
         else wrong = true;
       }
     }
-    unsigned lead = key[0] >= 0 ? 1u : 0u;              // the run of equal (a, b) that starts the lane's four
-    int e = 1;
-    for (; e < 4 && lead && key[e] == key[0]; ++e) ++lead;
-    wave_run_add(bins, key[0], lead);
-    for (; e < 4; ++e)
-      if (key[e] >= 0) atomicAdd(bins + key[e], 1u);
+    wave_quad_add(bins, key);                            // the run of equal (a, b) that starts the lane's four, the rest singly
   }
   const int64_t tail = head + 4 * nvec, nbytes = head + (n - tail);
   for (int64_t base = first; base < nbytes; base += stride) {

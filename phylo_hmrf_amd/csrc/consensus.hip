@@ -119,17 +119,6 @@ __device__ __forceinline__ uint32_t zero_bytes(uint32_t x) {
   return ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);
 }
 
-// the run of equal key that starts the lane's four nodes goes in through wave_run_add (x[e]: what node e adds), the nodes
-// after a change of key singly; key[e] < 0: the node adds nothing.  Every lane of the wave calls it.
-__device__ __forceinline__ void four_add(unsigned* bins, const int (&key)[4], const unsigned (&x)[4]) {
-  const bool r1 = key[0] >= 0 && key[1] == key[0], r2 = r1 && key[2] == key[0], r3 = r2 && key[3] == key[0];
-  const unsigned lead = (key[0] >= 0 ? x[0] : 0u) + (r1 ? x[1] : 0u) + (r2 ? x[2] : 0u) + (r3 ? x[3] : 0u);
-  wave_run_add(bins, key[0], lead);
-  if (!r1 && key[1] >= 0 && x[1]) atomicAdd(bins + key[1], x[1]);
-  if (!r2 && key[2] >= 0 && x[2]) atomicAdd(bins + key[2], x[2]);
-  if (!r3 && key[3] >= 0 && x[3]) atomicAdd(bins + key[3], x[3]);
-}
-
 // LDS of the vote kernel, in this order: M tiles of CONS_PER_TRIP bytes, M x 64 renumbering bytes, then the u32 tables
 // hist [K (M + 1)], pair [M M], bands [32 x 3], agree [am K K] for the maps [0, am)
 __global__ __launch_bounds__(256) void consensus_vote_kernel(ConsensusMaps maps, int M, int identity, int K, int64_t n, int W,
@@ -249,17 +238,17 @@ __global__ __launch_bounds__(256) void consensus_vote_kernel(ConsensusMaps maps,
         j = diagonal ? i : 0;
       }
     }
-    four_add(hist, key, one);
-    four_add(bands, band, one);
-    four_add(bands + 1, band, stable);
-    four_add(bands + 2, band, all);
+    wave_quad_add(hist, key, one);
+    wave_quad_add(bands, band, one);
+    wave_quad_add(bands + 1, band, stable);
+    wave_quad_add(bands + 2, band, all);
 
     // agree of the maps [0, am)
     for (int m = 0; m < am; ++m) {
       const uint32_t w = reinterpret_cast<const uint32_t*>(tiles + m * CONS_PER_TRIP)[tid];
 #pragma unroll
       for (int e = 0; e < 4; ++e) key[e] = state[e] >= 0 ? (m * K + state[e]) * K + (int)((w >> (8 * e)) & 63) : -1;
-      four_add(agree, key, one);
+      wave_quad_add(agree, key, one);
     }
 
     // pair: sixteen nodes of both maps per step
@@ -309,7 +298,7 @@ __global__ __launch_bounds__(256) void consensus_agree_kernel(ConsensusMaps maps
         const int c = (wc >> (8 * e)) & 0xff;
         key[e] = c < K ? (m * K + c) * K + (int)((w >> (8 * e)) & 63) : -1;
       }
-      four_add(agree, key, one);
+      wave_quad_add(agree, key, one);
     }
   }
   __syncthreads();

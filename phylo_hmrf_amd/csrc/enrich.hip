@@ -6,8 +6,9 @@
 //            of ENRICH_TILE_H storage rows by ENRICH_TILE_W storage columns, the tiles stride over a capped grid; a tile
 //            wholly outside the window is left without a load, a tile wholly inside it drops the per-cell test (as
 //            tracks.hip).  A HALF-wave holds one storage row: up to three head bytes to the next 4-byte boundary of the
-//            row's address, one 4-byte load per lane (four labels), up to three tail bytes (label_row, runs.h).  The tile's class and segment
-//            of every row and column bin are staged in LDS once (8 bytes a bin).
+//            row's address, one 4-byte load per lane (four labels), up to three tail bytes (label_row, runs.h; the tile's
+//            geometry and the row a half-wave counts: enrich_tiles.h, with enrich_null.hip).  The tile's class and segment of every
+//            row and column bin are staged in LDS once (8 bytes a bin).
 //            obs: u32 [P][K] in LDS for the workgroup's whole life, ONE atomic per run of equal (p, k) among consecutive
 //            lanes (wave_run_add; a run may cross the two rows of a wave, the sum is the same), flushed at the end with u64
 //            global atomics on the non-zero bins.
@@ -24,23 +25,13 @@
 //   A label >= K inside the window sets bit 0 of the flag word, a class >= C on a node inside the window bit 1; nodes outside
 //   the window are not inspected.
 
-#include "runs.h"
-
-#include <climits>
+#include "enrich_tiles.h"
 
 namespace phmrf {
 namespace {
 
 constexpr int ENRICH_GRID_CAP = 1024;    // workgroups of either kernel (enrich.py GRID_CAP)
-constexpr int ENRICH_TILE_H = 32;        // storage rows of a tile (enrich.py TILE_H)
-constexpr int ENRICH_TILE_W = 128;       // storage columns of a tile: 32 lanes x 4 labels (enrich.py TILE_W)
-constexpr int ENRICH_TILE_D = ENRICH_TILE_H + ENRICH_TILE_W - 1;   // distances of a tile
-constexpr int ENRICH_PAIRS_PER_WAVE = ENRICH_TILE_H / 8;           // a workgroup is four waves of two rows each
-constexpr int ENRICH_PER_SUPER = ENRICH_TILE_W / ENRICH_TILE_H;    // tiles of a square super-tile (diagonal blocks)
 constexpr int ENRICH_CHUNK = 512;        // cells of a diagonal a wave of the class kernel takes at a time
-constexpr int ENRICH_MAX_CLASSES = 8;
-constexpr int ENRICH_MAX_PAIRS = 2 * ENRICH_MAX_CLASSES * ENRICH_MAX_CLASSES;
-constexpr int BAD_LABEL = 1, BAD_CLASS = 2;
 
 // u32 words of a distance's row of the tile table: two states to a word, odd
 __host__ __device__ __forceinline__ int enrich_dist_stride(int K) { return ((K + 1) / 2) | 1; }
@@ -73,20 +64,9 @@ __global__ __launch_bounds__(256) void enrich_label_kernel(const uint8_t* __rest
   for (int64_t T = blockIdx.x; T < ntiles; T += gridDim.x) {
     WindowTile t;                                      // (its distances: nd <= ENRICH_TILE_D)
     if (!window_tile<ENRICH_TILE_H, ENRICH_TILE_W>(T, H, W, diagonal, per_row, dist0, d_lo, d_hi, &t)) continue;
-    // the half-wave's rows i0 + 2 wave + half, + 8, ...: every load of the tile is issued before the first count
     uint32_t word[ENRICH_PAIRS_PER_WAVE];
     int single[ENRICH_PAIRS_PER_WAVE];
-#pragma unroll
-    for (int u = 0; u < ENRICH_PAIRS_PER_WAVE; ++u) {
-      const int i = t.i0 + 2 * wave + half + 8 * u;
-      word[u] = 0;
-      single[u] = 0;
-      if (i < t.i1) {
-        const LabelRow r = label_row(labels, i, t.j0, t.j1, W, diagonal);
-        if (l32 < r.nvec) word[u] = *reinterpret_cast<const uint32_t*>(r.p + r.head + 4 * l32);
-        if (l32 < r.nbytes) single[u] = r.p[l32 < r.head ? l32 : r.tail + (l32 - r.head)];
-      }
-    }
+    load_tile_rows<8>(labels, t, W, diagonal, 2 * wave + half, l32, word, single);   // a half-wave per row
     if (threadIdx.x < ENRICH_TILE_W) {
       const int j = t.j0 + threadIdx.x;
       if (j < t.j1) col_info[threadIdx.x] = make_int2(col_class[j], col_seg ? col_seg[j] : -1);
@@ -100,8 +80,7 @@ __global__ __launch_bounds__(256) void enrich_label_kernel(const uint8_t* __rest
       if (t.i0 + 2 * wave + 8 * u >= t.i1) break;       // the same for the wave; its second row may still be absent
       const int i = t.i0 + 2 * wave + half + 8 * u;
       const bool present = i < t.i1;
-      LabelRow r = label_row(labels, present ? i : t.i0, t.j0, t.j1, W, diagonal);
-      if (!present) r.nvec = r.nbytes = 0;
+      const LabelRow r = present_row(labels, t, i, present, W, diagonal);
       const int2 mine = row_info[present ? i - t.i0 : 0];
       const int x0 = dist0 - i;                         // the cell's distance is |x0 + j|
       // one cell: -1 outside the window, with a label >= K or a class >= C, else its obs bin; the distance table takes it here
@@ -117,9 +96,8 @@ __global__ __launch_bounds__(256) void enrich_label_kernel(const uint8_t* __rest
           wrong |= BAD_CLASS;
           return -1;
         }
-        const int same = (mine.y >= 0 && mine.y == other.y) ? 1 : 0;
         atomicAdd(dist_tab + (d - t.near) * ds + (s >> 1), 1u << (16 * (s & 1)));
-        return ((mine.x * C + other.x) * 2 + same) * K + s;
+        return pair_bin(mine, other, C) * K + s;
       };
       {
         int key[4] = {-1, -1, -1, -1};
@@ -129,16 +107,11 @@ __global__ __launch_bounds__(256) void enrich_label_kernel(const uint8_t* __rest
 #pragma unroll
           for (int e = 0; e < 4; ++e) key[e] = cell((int)((w >> (8 * e)) & 0xff), j + ((e + rot) & 3));
         }
-        unsigned lead = key[0] >= 0 ? 1u : 0u;          // the lane's cells in the bin of its first
-        int e = 1;
-        for (; e < 4 && lead && key[e] == key[0]; ++e) ++lead;
-        wave_run_add(obs_tab, key[0], lead);
-        for (; e < 4; ++e)
-          if (key[e] >= 0) atomicAdd(obs_tab + key[e], 1u);
+        wave_quad_add(obs_tab, key);
       }
       {
         int key = -1;
-        if (l32 < r.nbytes) key = cell(single[u], r.ja + (l32 < r.head ? l32 : r.tail + (l32 - r.head)));
+        if (l32 < r.nbytes) key = cell(single[u], r.ja + r.byte_at(l32));
         wave_run_add(obs_tab, key, key >= 0 ? 1u : 0u);
       }
     }
@@ -163,8 +136,7 @@ __global__ __launch_bounds__(256) void enrich_label_kernel(const uint8_t* __rest
   if (wrong) atomicOr(bad, wrong);
 }
 
-// cat_dist: u32 [D][2 C C], row 0 the distance tab_lo.  The diagonals: x = xa + t for t < na, x = xb + (t - na) for the nb
-// after them; `slots` chunks of ENRICH_CHUNK rows cover the longest diagonal; item = t slots + slot.
+// cat_dist: u32 [D][2 C C], row 0 the distance tab_lo.  The diagonals and their chunks of ENRICH_CHUNK rows: diagonal_chunk.
 __global__ __launch_bounds__(256) void enrich_class_kernel(int H, int W, int diagonal, int dist0, int C,
                                                            const uint8_t* __restrict__ row_class,
                                                            const uint8_t* __restrict__ col_class,
@@ -179,14 +151,8 @@ __global__ __launch_bounds__(256) void enrich_class_kernel(int H, int W, int dia
   __syncthreads();
   bool wrong = false;
   for (int64_t item = (int64_t)blockIdx.x * 4 + wave; item < nitems; item += (int64_t)gridDim.x * 4) {
-    const int t = (int)(item / slots), slot = (int)(item - (int64_t)t * slots);
-    const int x = t < na ? xa + t : xb + (t - na);
-    // the rows i of the diagonal: 0 <= i < H and 0 <= j = i + x - dist0 < W
-    const int shift = x - dist0;                        // in [-(H - 1), W - 1]
-    const int i_lo = shift < 0 ? -shift : 0, i_hi = W - shift < H ? W - shift : H;
-    const int64_t a64 = (int64_t)i_lo + (int64_t)slot * ENRICH_CHUNK;
-    if (a64 >= i_hi) continue;                          // (the same for the wave)
-    const int a = (int)a64, b = i_hi - a > ENRICH_CHUNK ? a + ENRICH_CHUNK : i_hi;
+    int x, shift, a, b;
+    if (!diagonal_chunk<ENRICH_CHUNK>(item, slots, xa, na, xb, dist0, H, W, &x, &shift, &a, &b)) continue;
     for (int base = a; base < b; base += 64) {
       const int i = base + lane;
       int key = -1;
@@ -197,7 +163,7 @@ __global__ __launch_bounds__(256) void enrich_class_kernel(int H, int W, int dia
           wrong = true;
         } else {
           const int rs = row_seg ? row_seg[i] : -1, cs = col_seg ? col_seg[j] : -1;
-          key = (rc * C + cc) * 2 + ((rs >= 0 && rs == cs) ? 1 : 0);
+          key = pair_bin(make_int2(rc, rs), make_int2(cc, cs), C);
         }
       }
       wave_run_add(tab, key, key >= 0 ? 1u : 0u);
@@ -227,43 +193,28 @@ int phmrf_pair_enrichment(const uint8_t* labels_dev, int H, int W, int diagonal,
                           int64_t* obs_host, int64_t* state_dist_host, int64_t* cat_dist_host, void* hip_stream) {
   PHMRF_CHECK(labels_dev && row_class_dev && obs_host && state_dist_host && cat_dist_host, PHMRF_ERR_INVALID,
               "NULL labels, row classes or output table");
-  PHMRF_CHECK(diagonal == 0 || diagonal == 1, PHMRF_ERR_INVALID, "diagonal must be 0 or 1");
+  int64_t n;
+  PHMRF_TRY(check_region(H, W, diagonal, &n));
   PHMRF_CHECK(diagonal || col_class_dev_or_null, PHMRF_ERR_INVALID, "an off-diagonal block needs column classes");
   PHMRF_CHECK(diagonal || (row_seg_dev_or_null == nullptr) == (col_seg_dev_or_null == nullptr), PHMRF_ERR_INVALID,
               "an off-diagonal block needs row and column segments, or neither");
-  PHMRF_CHECK(H >= 1 && W >= 1, PHMRF_ERR_INVALID, "H and W must be >= 1");
   PHMRF_CHECK(K >= 1 && C >= 1, PHMRF_ERR_INVALID, "K and C must be >= 1");
   PHMRF_CHECK(D >= 0 && d_lo >= 0, PHMRF_ERR_INVALID, "D and d_lo must be >= 0");
-  PHMRF_CHECK(!diagonal || H == W, PHMRF_ERR_INVALID, "a diagonal block is square (H == W)");
   PHMRF_CHECK(!diagonal || dist0 == 0, PHMRF_ERR_INVALID, "a diagonal block has dist0 == 0");
-  PHMRF_CHECK(d_min >= 0, PHMRF_ERR_INVALID, "d_min must be >= 0");
-  PHMRF_CHECK(d_max == -1 || d_max >= d_min, PHMRF_ERR_INVALID, "d_max must be >= d_min, or -1 for no upper limit");
-  PHMRF_CHECK(K <= 64, PHMRF_ERR_UNSUPPORTED, "K must be <= 64");
+  PHMRF_TRY(check_window(d_min, d_max));
+  PHMRF_TRY(check_states(K));                          // (its upper limit)
   PHMRF_CHECK(C <= ENRICH_MAX_CLASSES, PHMRF_ERR_UNSUPPORTED, "C must be <= 8");
-  const int64_t n = grid_row_first<int64_t>(H, W, diagonal);
   PHMRF_TRY(check_nodes(n, "n must be below 2^31 - 64"));
-  PHMRF_CHECK(dist0 > -((int64_t)1 << 31) && dist0 < ((int64_t)1 << 31) &&
-                  (dist0 < 0 ? -dist0 : dist0) + H + W < ((int64_t)1 << 31),
-              PHMRF_ERR_UNSUPPORTED, "|dist0| + H + W must be below 2^31");
+  PHMRF_TRY(check_span(dist0, H, W));
   const int P = 2 * C * C;
   PHMRF_CHECK(D < ((int64_t)1 << 31) && D * (K > P ? K : P) < ((int64_t)1 << 31), PHMRF_ERR_UNSUPPORTED,
               "D max(K, 2 C C) must be below 2^31");
-  // the signed diagonals x = dist0 + j - i of the region, and of them the ones inside the window: xa .. xa + na - 1 >= 0 and
-  // xb .. xb + nb - 1 < 0.  Every distance is below INT_MAX: a d_min up there leaves nothing inside, a d_max up there is no limit.
-  const int64_t w_lo = d_min < INT_MAX ? d_min : INT_MAX, w_hi = (d_max == -1 || d_max > INT_MAX) ? INT_MAX : d_max;
-  const int64_t x_lo = diagonal ? 0 : dist0 - (H - 1), x_hi = diagonal ? H - 1 : dist0 + (W - 1);
-  const int64_t xa = x_lo > w_lo ? x_lo : w_lo, xa_end = x_hi < w_hi ? x_hi : w_hi;
-  const int64_t xb = x_lo > -w_hi ? x_lo : -w_hi, xb_end = x_hi < -(w_lo > 1 ? w_lo : 1) ? x_hi : -(w_lo > 1 ? w_lo : 1);
-  const int64_t na = xa_end >= xa ? xa_end - xa + 1 : 0, nb = xb_end >= xb ? xb_end - xb + 1 : 0;
-  if (na + nb > 0) {                                   // the distances inside the window: one range, the table must hold it
-    int64_t lo = INT64_MAX, hi = -1;
-    if (na) lo = xa, hi = xa_end;
-    if (nb) lo = -xb_end < lo ? -xb_end : lo, hi = -xb > hi ? -xb : hi;
-    PHMRF_CHECK(d_lo <= lo && hi < d_lo + D, PHMRF_ERR_INVALID, "the table [d_lo, d_lo + D) does not hold every distance inside the window");
-  }
+  const IntWindow win = int_window(d_min, d_max);
+  WindowDiagonals dg;
+  PHMRF_TRY(window_diagonals(H, W, diagonal, dist0, win, d_lo, D, &dg));
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   const size_t n_obs = (size_t)P * K, n_sd = (size_t)D * K, n_cd = (size_t)D * P;
-  if (na + nb == 0) {                                  // nothing inside the window
+  if (dg.na + dg.nb == 0) {                            // nothing inside the window
     for (size_t t = 0; t < n_obs; ++t) obs_host[t] = 0;
     for (size_t t = 0; t < n_sd; ++t) state_dist_host[t] = 0;
     for (size_t t = 0; t < n_cd; ++t) cat_dist_host[t] = 0;
@@ -271,11 +222,10 @@ int phmrf_pair_enrichment(const uint8_t* labels_dev, int H, int W, int diagonal,
   }
   const uint8_t* const col_class = diagonal ? row_class_dev : col_class_dev_or_null;
   const int32_t* const col_seg = diagonal ? row_seg_dev_or_null : col_seg_dev_or_null;
-  const int per_row = (W + ENRICH_TILE_W - 1) / ENRICH_TILE_W;
-  const int64_t ntiles = diagonal ? (int64_t)ENRICH_PER_SUPER * grid_row_first<int64_t>(per_row, per_row, 1)
-                                  : (int64_t)((H + ENRICH_TILE_H - 1) / ENRICH_TILE_H) * per_row;
+  int per_row;
+  const int64_t ntiles = window_tile_count<ENRICH_TILE_H, ENRICH_TILE_W>(H, W, diagonal, &per_row);
   const int slots = ((H < W ? H : W) + ENRICH_CHUNK - 1) / ENRICH_CHUNK;
-  const int64_t nitems = (na + nb) * slots;
+  const int64_t nitems = ((int64_t)dg.na + dg.nb) * slots;
 
   // one allocation and one memset, whatever the call's size: obs u64 [P K] | state_dist u32 [D K] | cat_dist u32 [D P] | the flag word
   Buffers buf;
@@ -287,11 +237,11 @@ int phmrf_pair_enrichment(const uint8_t* labels_dev, int H, int W, int diagonal,
   int* const flag = reinterpret_cast<int*>(cat_dist + n_cd);
   PHMRF_HIP(hipMemsetAsync(all, 0, (n_obs + (n_u32 + 1) / 2) * sizeof(unsigned long long), st));
   hipLaunchKernelGGL(enrich_label_kernel, dim3(grid_of(ntiles, 1, ENRICH_GRID_CAP)), dim3(256), enrich_lds_bytes(K, C), st, labels_dev,
-                     H, W, diagonal, (int)dist0, K, C, row_class_dev, col_class, row_seg_dev_or_null, col_seg, (int)w_lo, (int)w_hi,
+                     H, W, diagonal, (int)dist0, K, C, row_class_dev, col_class, row_seg_dev_or_null, col_seg, win.lo, win.hi,
                      (int)d_lo, per_row, ntiles, all, state_dist, flag);
   PHMRF_HIP(hipGetLastError());
   hipLaunchKernelGGL(enrich_class_kernel, dim3(grid_of(nitems, 4, ENRICH_GRID_CAP)), dim3(256), 0, st, H, W, diagonal, (int)dist0, C,
-                     row_class_dev, col_class, row_seg_dev_or_null, col_seg, (int)xa, (int)na, (int)xb, slots, nitems, (int)d_lo,
+                     row_class_dev, col_class, row_seg_dev_or_null, col_seg, dg.xa, dg.na, dg.xb, slots, nitems, (int)d_lo,
                      cat_dist, flag);
   PHMRF_HIP(hipGetLastError());
   int bad = 0;

@@ -3,7 +3,7 @@
 // 2^-24 fixed point.  Integer arithmetic throughout: no result depends on the order in which the atomics land.
 //
 //   counting     obs[t][p][k] over the stored nodes INSIDE the distance window.  enrich.hip's tile geometry (a tile of
-//                ENRICH_TILE_H storage rows by ENRICH_TILE_W storage columns, a half-wave per row: label_row, window_tile,
+//                ENRICH_TILE_H storage rows by ENRICH_TILE_W storage columns, a half-wave per row: enrich_tiles.h; label_row, window_tile,
 //                wave_run_add of runs.h).  A workgroup owns a GROUP of up to TS shifts (blockIdx.y; null_group_shifts: as many
 //                as fit the 64 KB of LDS a launch gets without asking, at most NULL_MAX_GROUP) and strides over the tiles:
 //                a tile's labels are loaded ONCE into registers and counted against every shift of the group.  Per tile the
@@ -21,29 +21,20 @@
 //   A label >= K inside the window sets bit 0 of the flag word, a class >= C on a node inside the window under one of the
 //   call's shifts bit 1; nodes outside the window are not inspected.
 
-#include "runs.h"
-
-#include <climits>
+#include "enrich_tiles.h"
 
 namespace phmrf {
 namespace {
 
 constexpr int NULL_GRID_CAP = 1024;      // workgroups of the counting kernel (enrich.py NULL_GRID_CAP)
 constexpr int NULL_CLASS_CAP = 4096;     // workgroups of the expectation kernel (enrich.py NULL_CLASS_CAP)
-constexpr int NULL_TILE_H = 32;          // enrich.hip's tile: storage rows ...
-constexpr int NULL_TILE_W = 128;         // ... and storage columns, 32 lanes x 4 labels
-constexpr int NULL_BINS = NULL_TILE_H + NULL_TILE_W;           // bins of a tile whose (class, segment) is staged per shift
-constexpr int NULL_PAIRS_PER_WAVE = NULL_TILE_H / 8;           // a workgroup is four waves of two rows each
-constexpr int NULL_PER_SUPER = NULL_TILE_W / NULL_TILE_H;      // tiles of a square super-tile (diagonal blocks)
+constexpr int NULL_BINS = ENRICH_TILE_H + ENRICH_TILE_W;       // bins of a tile whose (class, segment) is staged per shift
 constexpr int NULL_CHUNK = 512;          // cells of a diagonal a wave of the expectation kernel takes at a time
-constexpr int NULL_MAX_CLASSES = 8;
-constexpr int NULL_MAX_PAIRS = 2 * NULL_MAX_CLASSES * NULL_MAX_CLASSES;
 constexpr int NULL_LDS_BYTES = 65536;    // LDS of the counting kernel (enrich.py NULL_LDS_BYTES)
 constexpr int NULL_MAX_GROUP = 16;       // shifts of a group at most (enrich.py NULL_MAX_GROUP)
 constexpr int NULL_ACC_BYTES = 49152;    // the expectation kernel's u64 [P][Kc] table at most
 constexpr int NULL_MAX_SHIFTS = 4096;
 constexpr unsigned NULL_WEIGHT_ONE = 1u << 24;
-constexpr int BAD_LABEL = 1, BAD_CLASS = 2;
 
 // shifts of a group (enrich.py null_group): a count table of u32 [2 C C][K] and 8 bytes for each of the tile's bins per shift
 inline int null_group_shifts(int K, int C) {
@@ -77,26 +68,15 @@ __global__ __launch_bounds__(256) void enrich_null_label_kernel(const uint8_t* _
   int wrong = 0;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     WindowTile t;
-    if (!window_tile<NULL_TILE_H, NULL_TILE_W>(tile, H, W, diagonal, per_row, dist0, d_lo, d_hi, &t)) continue;
-    // the half-wave's rows i0 + 2 wave + half, + 8, ...: every load of the tile is issued before the first count
-    uint32_t word[NULL_PAIRS_PER_WAVE];
-    int single[NULL_PAIRS_PER_WAVE];
-#pragma unroll
-    for (int u = 0; u < NULL_PAIRS_PER_WAVE; ++u) {
-      const int i = t.i0 + 2 * wave + half + 8 * u;
-      word[u] = 0;
-      single[u] = 0;
-      if (i < t.i1) {
-        const LabelRow r = label_row(labels, i, t.j0, t.j1, W, diagonal);
-        if (l32 < r.nvec) word[u] = *reinterpret_cast<const uint32_t*>(r.p + r.head + 4 * l32);
-        if (l32 < r.nbytes) single[u] = r.p[l32 < r.head ? l32 : r.tail + (l32 - r.head)];
-      }
-    }
+    if (!window_tile<ENRICH_TILE_H, ENRICH_TILE_W>(tile, H, W, diagonal, per_row, dist0, d_lo, d_hi, &t)) continue;
+    uint32_t word[ENRICH_PAIRS_PER_WAVE];
+    int single[ENRICH_PAIRS_PER_WAVE];
+    load_tile_rows<8>(labels, t, W, diagonal, 2 * wave + half, l32, word, single);   // a half-wave per row
     for (int x = threadIdx.x; x < mine_ts * NULL_BINS; x += 256) {
       const int q = x / NULL_BINS, b = x - q * NULL_BINS;
       const unsigned s = (unsigned)shifts[t0 + q];
-      const bool column = b < NULL_TILE_W;
-      const int at = column ? t.j0 + b : t.i0 + (b - NULL_TILE_W);
+      const bool column = b < ENRICH_TILE_W;
+      const int at = column ? t.j0 + b : t.i0 + (b - ENRICH_TILE_W);
       if (at < (column ? t.j1 : t.i1)) {
         const unsigned g = wrapped((column ? col0 : row0) + (unsigned)at, s, B);
         info[x] = make_int2(cls[g], seg ? seg[g] : -1);
@@ -104,12 +84,11 @@ __global__ __launch_bounds__(256) void enrich_null_label_kernel(const uint8_t* _
     }
     __syncthreads();                                   // (the first tile: the zeroed tables too)
 #pragma unroll
-    for (int u = 0; u < NULL_PAIRS_PER_WAVE; ++u) {
+    for (int u = 0; u < ENRICH_PAIRS_PER_WAVE; ++u) {
       if (t.i0 + 2 * wave + 8 * u >= t.i1) break;       // the same for the wave; its second row may still be absent
       const int i = t.i0 + 2 * wave + half + 8 * u;
       const bool present = i < t.i1;
-      LabelRow r = label_row(labels, present ? i : t.i0, t.j0, t.j1, W, diagonal);
-      if (!present) r.nvec = r.nbytes = 0;
+      const LabelRow r = present_row(labels, t, i, present, W, diagonal);
       const int x0 = dist0 - i;                         // the cell's distance is |x0 + j|
       // one cell, whatever the shift: its state, -1 outside the window or with a label >= K
       auto state_of = [&](int s, int j) -> int {
@@ -123,14 +102,14 @@ __global__ __launch_bounds__(256) void enrich_null_label_kernel(const uint8_t* _
       };
       int st[4] = {-1, -1, -1, -1}, st1 = -1;
       const int jv = r.ja + r.head + 4 * l32 - t.j0;    // the lane's first word column, from the tile's first
-      const int j1 = r.ja + (l32 < r.head ? l32 : r.tail + (l32 - r.head)) - t.j0;
+      const int j1 = r.ja + r.byte_at(l32) - t.j0;
       if (l32 < r.nvec) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) st[e] = state_of((int)((word[u] >> (8 * e)) & 0xff), t.j0 + jv + e);
       }
       if (l32 < r.nbytes) st1 = state_of(single[u], t.j0 + j1);
       const bool bytes = __any(st1 >= 0);
-      const int ri = NULL_TILE_W + (present ? i - t.i0 : 0);
+      const int ri = ENRICH_TILE_W + (present ? i - t.i0 : 0);
       for (int q = 0; q < mine_ts; ++q) {
         const int2* const inf = info + q * NULL_BINS;
         unsigned* const tab = tabs + q * nobs;
@@ -142,19 +121,13 @@ __global__ __launch_bounds__(256) void enrich_null_label_kernel(const uint8_t* _
             wrong |= BAD_CLASS;
             return -1;
           }
-          const int same = (mine.y >= 0 && mine.y == other.y) ? 1 : 0;
-          return ((mine.x * C + other.x) * 2 + same) * K + s;
+          return pair_bin(mine, other, C) * K + s;
         };
         {
           int key[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) key[e] = st[e] >= 0 ? bin(st[e], jv + e) : -1;
-          unsigned lead = key[0] >= 0 ? 1u : 0u;        // the lane's cells in the bin of its first
-          int e = 1;
-          for (; e < 4 && lead && key[e] == key[0]; ++e) ++lead;
-          wave_run_add(tab, key[0], lead);
-          for (; e < 4; ++e)
-            if (key[e] >= 0) atomicAdd(tab + key[e], 1u);
+          wave_quad_add(tab, key);
         }
         if (bytes) {                                    // (the same for the wave)
           const int key = st1 >= 0 ? bin(st1, j1) : -1;
@@ -173,8 +146,7 @@ __global__ __launch_bounds__(256) void enrich_null_label_kernel(const uint8_t* _
 }
 
 // expq: u64 [T][2 C C][K]; weight: u32 [D][K], row 0 the distance tab_lo.  blockIdx.y: the shift; blockIdx.z: the states
-// [Kc blockIdx.z, + Kc) below K.  The diagonals: x = xa + t for t < na, x = xb + (t - na) for the nb after them; `slots` chunks
-// of NULL_CHUNK rows cover the longest diagonal; item = t slots + slot.
+// [Kc blockIdx.z, + Kc) below K.  The diagonals and their chunks of NULL_CHUNK rows: diagonal_chunk.
 __global__ __launch_bounds__(256) void enrich_null_class_kernel(int H, int W, int diagonal, int dist0, int K, int C,
                                                                 const uint8_t* __restrict__ cls, const int32_t* __restrict__ seg,
                                                                 unsigned row0, unsigned col0, unsigned B,
@@ -182,25 +154,19 @@ __global__ __launch_bounds__(256) void enrich_null_class_kernel(int H, int W, in
                                                                 int64_t nitems, int tab_lo, const unsigned* __restrict__ weight, int Kc,
                                                                 unsigned long long* __restrict__ expq, int* __restrict__ bad) {
   extern __shared__ unsigned long long null_acc[];    // [P][Kc]
-  __shared__ unsigned tabs[4][NULL_MAX_PAIRS];
+  __shared__ unsigned tabs[4][ENRICH_MAX_PAIRS];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned* const tab = tabs[wave];
   const int P = 2 * C * C;
   const int k0 = blockIdx.z * Kc, kc = K - k0 < Kc ? K - k0 : Kc;
   const unsigned s = (unsigned)shifts[blockIdx.y];
-  for (int q = lane; q < NULL_MAX_PAIRS; q += 64) tab[q] = 0;
+  for (int q = lane; q < ENRICH_MAX_PAIRS; q += 64) tab[q] = 0;
   for (int x = threadIdx.x; x < P * Kc; x += 256) null_acc[x] = 0;
   __syncthreads();
   bool wrong = false;
   for (int64_t item = (int64_t)blockIdx.x * 4 + wave; item < nitems; item += (int64_t)gridDim.x * 4) {
-    const int t = (int)(item / slots), slot = (int)(item - (int64_t)t * slots);
-    const int x = t < na ? xa + t : xb + (t - na);
-    // the rows i of the diagonal: 0 <= i < H and 0 <= j = i + x - dist0 < W
-    const int shift = x - dist0;                        // in [-(H - 1), W - 1]
-    const int i_lo = shift < 0 ? -shift : 0, i_hi = W - shift < H ? W - shift : H;
-    const int64_t a64 = (int64_t)i_lo + (int64_t)slot * NULL_CHUNK;
-    if (a64 >= i_hi) continue;                          // (the same for the wave)
-    const int a = (int)a64, b = i_hi - a > NULL_CHUNK ? a + NULL_CHUNK : i_hi;
+    int x, shift, a, b;
+    if (!diagonal_chunk<NULL_CHUNK>(item, slots, xa, na, xb, dist0, H, W, &x, &shift, &a, &b)) continue;
     for (int base = a; base < b; base += 64) {
       const int i = base + lane;
       int key = -1;
@@ -211,7 +177,7 @@ __global__ __launch_bounds__(256) void enrich_null_class_kernel(int H, int W, in
           wrong = true;
         } else {
           const int rs = seg ? seg[gi] : -1, cs = seg ? seg[gj] : -1;
-          key = (rc * C + cc) * 2 + ((rs >= 0 && rs == cs) ? 1 : 0);
+          key = pair_bin(make_int2(rc, rs), make_int2(cc, cs), C);
         }
       }
       wave_run_add(tab, key, key >= 0 ? 1u : 0u);
@@ -255,27 +221,24 @@ int phmrf_pair_enrichment_null(const uint8_t* labels_dev, int H, int W, int diag
                                const uint32_t* weight_host, int64_t* obs_host, int64_t* expq_host, void* hip_stream) {
   PHMRF_CHECK(labels_dev && chrom_class_dev && shifts_host && weight_host && obs_host && expq_host, PHMRF_ERR_INVALID,
               "NULL labels, classes, shifts, weights or output table");
-  PHMRF_CHECK(diagonal == 0 || diagonal == 1, PHMRF_ERR_INVALID, "diagonal must be 0 or 1");
-  PHMRF_CHECK(H >= 1 && W >= 1, PHMRF_ERR_INVALID, "H and W must be >= 1");
+  int64_t n;
+  PHMRF_TRY(check_region(H, W, diagonal, &n));
   PHMRF_CHECK(K >= 1 && C >= 1, PHMRF_ERR_INVALID, "K and C must be >= 1");
   PHMRF_CHECK(T >= 1, PHMRF_ERR_INVALID, "T must be >= 1");
   PHMRF_CHECK(D >= 0 && d_lo >= 0, PHMRF_ERR_INVALID, "D and d_lo must be >= 0");
-  PHMRF_CHECK(!diagonal || H == W, PHMRF_ERR_INVALID, "a diagonal block is square (H == W)");
   PHMRF_CHECK(!diagonal || row0 == col0, PHMRF_ERR_INVALID, "a diagonal block has row0 == col0");
   PHMRF_CHECK(row0 >= 0 && col0 >= 0 && row0 <= B - H && col0 <= B - W, PHMRF_ERR_INVALID,
               "the region's rows and columns must lie inside the chromosome's B bins");
-  PHMRF_CHECK(d_min >= 0, PHMRF_ERR_INVALID, "d_min must be >= 0");
-  PHMRF_CHECK(d_max == -1 || d_max >= d_min, PHMRF_ERR_INVALID, "d_max must be >= d_min, or -1 for no upper limit");
-  PHMRF_CHECK(K <= 64, PHMRF_ERR_UNSUPPORTED, "K must be <= 64");
-  PHMRF_CHECK(C <= NULL_MAX_CLASSES, PHMRF_ERR_UNSUPPORTED, "C must be <= 8");
+  PHMRF_TRY(check_window(d_min, d_max));
+  PHMRF_TRY(check_states(K));                          // (its upper limit)
+  PHMRF_CHECK(C <= ENRICH_MAX_CLASSES, PHMRF_ERR_UNSUPPORTED, "C must be <= 8");
   PHMRF_CHECK(T <= NULL_MAX_SHIFTS, PHMRF_ERR_UNSUPPORTED, "T must be <= 4096");
   const int P = 2 * C * C;
   PHMRF_CHECK((int64_t)T * P * K < ((int64_t)1 << 26), PHMRF_ERR_UNSUPPORTED, "T 2 C C K must be below 2^26");
   PHMRF_CHECK(B < ((int64_t)1 << 31), PHMRF_ERR_UNSUPPORTED, "B must be below 2^31");
-  const int64_t n = grid_row_first<int64_t>(H, W, diagonal);
   PHMRF_TRY(check_nodes(n, "n must be below 2^31 - 64"));
   const int64_t dist0 = col0 - row0;                   // (|dist0| + H + W < 2 B + ... : B < 2^31 does not bound it)
-  PHMRF_CHECK((dist0 < 0 ? -dist0 : dist0) + H + W < ((int64_t)1 << 31), PHMRF_ERR_UNSUPPORTED, "|dist0| + H + W must be below 2^31");
+  PHMRF_TRY(check_span(dist0, H, W));
   PHMRF_CHECK(D < ((int64_t)1 << 31) && D * (K > P ? K : P) < ((int64_t)1 << 31), PHMRF_ERR_UNSUPPORTED,
               "D max(K, 2 C C) must be below 2^31");
   for (int t = 0; t < T; ++t)
@@ -283,28 +246,19 @@ int phmrf_pair_enrichment_null(const uint8_t* labels_dev, int H, int W, int diag
   const size_t n_w = (size_t)D * K;
   for (size_t t = 0; t < n_w; ++t) PHMRF_CHECK(weight_host[t] <= NULL_WEIGHT_ONE, PHMRF_ERR_INVALID, "a weight is above 2^24");
   // the signed diagonals inside the window and the table's range: as phmrf_pair_enrichment
-  const int64_t w_lo = d_min < INT_MAX ? d_min : INT_MAX, w_hi = (d_max == -1 || d_max > INT_MAX) ? INT_MAX : d_max;
-  const int64_t x_lo = diagonal ? 0 : dist0 - (H - 1), x_hi = diagonal ? H - 1 : dist0 + (W - 1);
-  const int64_t xa = x_lo > w_lo ? x_lo : w_lo, xa_end = x_hi < w_hi ? x_hi : w_hi;
-  const int64_t xb = x_lo > -w_hi ? x_lo : -w_hi, xb_end = x_hi < -(w_lo > 1 ? w_lo : 1) ? x_hi : -(w_lo > 1 ? w_lo : 1);
-  const int64_t na = xa_end >= xa ? xa_end - xa + 1 : 0, nb = xb_end >= xb ? xb_end - xb + 1 : 0;
-  if (na + nb > 0) {
-    int64_t lo = INT64_MAX, hi = -1;
-    if (na) lo = xa, hi = xa_end;
-    if (nb) lo = -xb_end < lo ? -xb_end : lo, hi = -xb > hi ? -xb : hi;
-    PHMRF_CHECK(d_lo <= lo && hi < d_lo + D, PHMRF_ERR_INVALID, "the table [d_lo, d_lo + D) does not hold every distance inside the window");
-  }
+  const IntWindow win = int_window(d_min, d_max);
+  WindowDiagonals dg;
+  PHMRF_TRY(window_diagonals(H, W, diagonal, dist0, win, d_lo, D, &dg));
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   const size_t n_tab = (size_t)T * P * K;
-  if (na + nb == 0) {                                  // nothing inside the window
+  if (dg.na + dg.nb == 0) {                            // nothing inside the window
     for (size_t t = 0; t < n_tab; ++t) obs_host[t] = expq_host[t] = 0;
     return PHMRF_OK;
   }
-  const int per_row = (W + NULL_TILE_W - 1) / NULL_TILE_W;
-  const int64_t ntiles = diagonal ? (int64_t)NULL_PER_SUPER * grid_row_first<int64_t>(per_row, per_row, 1)
-                                  : (int64_t)((H + NULL_TILE_H - 1) / NULL_TILE_H) * per_row;
+  int per_row;
+  const int64_t ntiles = window_tile_count<ENRICH_TILE_H, ENRICH_TILE_W>(H, W, diagonal, &per_row);
   const int slots = ((H < W ? H : W) + NULL_CHUNK - 1) / NULL_CHUNK;
-  const int64_t nitems = (na + nb) * slots;
+  const int64_t nitems = ((int64_t)dg.na + dg.nb) * slots;
   const int ts = null_group_shifts(K, C), groups = (T + ts - 1) / ts;
   const int splits = (8 * P * K + NULL_ACC_BYTES - 1) / NULL_ACC_BYTES, Kc = (K + splits - 1) / splits;
 
@@ -323,13 +277,13 @@ int phmrf_pair_enrichment_null(const uint8_t* labels_dev, int H, int W, int diag
   const int per_group = NULL_GRID_CAP / groups > 1 ? NULL_GRID_CAP / groups : 1;
   hipLaunchKernelGGL(enrich_null_label_kernel, dim3(grid_of(ntiles, 1, per_group), groups), dim3(256),
                      (size_t)ts * (8 * NULL_BINS + 4 * (size_t)P * K), st, labels_dev, H, W, diagonal, (int)dist0, K, C, chrom_class_dev,
-                     chrom_seg_dev_or_null, (unsigned)row0, (unsigned)col0, (unsigned)B, shifts, T, ts, (int)w_lo, (int)w_hi, per_row,
+                     chrom_seg_dev_or_null, (unsigned)row0, (unsigned)col0, (unsigned)B, shifts, T, ts, win.lo, win.hi, per_row,
                      ntiles, all, flag);
   PHMRF_HIP(hipGetLastError());
   const int per_shift = NULL_CLASS_CAP / T > 1 ? NULL_CLASS_CAP / T : 1;
   hipLaunchKernelGGL(enrich_null_class_kernel, dim3(grid_of(nitems, 4, per_shift), T, splits), dim3(256), (size_t)8 * P * Kc, st, H, W,
                      diagonal, (int)dist0, K, C, chrom_class_dev, chrom_seg_dev_or_null, (unsigned)row0, (unsigned)col0, (unsigned)B,
-                     shifts, (int)xa, (int)na, (int)xb, slots, nitems, (int)d_lo, weight, Kc, expq, flag);
+                     shifts, dg.xa, dg.na, dg.xb, slots, nitems, (int)d_lo, weight, Kc, expq, flag);
   PHMRF_HIP(hipGetLastError());
   int bad = 0;
   PHMRF_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));

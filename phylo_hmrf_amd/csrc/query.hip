@@ -99,25 +99,18 @@ __global__ __launch_bounds__(64 * RECT_WAVES) void rect_states_kernel(const uint
         const int64_t v0 = r.p - labels;
         uint32_t word = 0;
         int single = 0;
-        if (lane < r.nvec) word = *reinterpret_cast<const uint32_t*>(r.p + r.head + 4 * lane);
-        const int at = lane < r.head ? lane : r.tail + (lane - r.head);
-        if (lane < r.nbytes) single = r.p[at];
+        load_row(r, lane, &word, &single);
         if (r.nvec > 0) {
           int key[4] = {-1, -1, -1, -1};
           if (lane < r.nvec) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) key[e] = cell((int)((word >> (8 * e)) & 0xff), v0 + r.head + 4 * lane + e, f);
           }
-          unsigned lead = key[0] >= 0 ? 1u : 0u;         // the lane's cells in the state of its first
-          int e = 1;
-          for (; e < 4 && lead && key[e] == key[0]; ++e) ++lead;
-          wave_run_add(hist, key[0], lead);
-          for (; e < 4; ++e)
-            if (key[e] >= 0) atomicAdd(hist + key[e], 1u);
+          wave_quad_add(hist, key);
         }
         if (r.nbytes > 0) {
           int key = -1;
-          if (lane < r.nbytes) key = cell(single, v0 + at, f);
+          if (lane < r.nbytes) key = cell(single, v0 + r.byte_at(lane), f);
           wave_run_add(hist, key, key >= 0 ? 1u : 0u);
         }
       }

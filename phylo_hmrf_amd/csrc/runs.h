@@ -1,11 +1,13 @@
-// What the post-processing's kernel files share (smooth.hip, compare.hip, profile.hip, domains.hip, tracks.hip, enrich.hip):
-// the capped grid, the wave helpers of their integer accumulations -- one atomic per RUN of equal destination among
-// consecutive lanes, because state maps are piecewise constant --, the split of a label row into aligned words and the tiles of
-// a distance window (tracks.hip, enrich.hip), the full-matrix area of a grid component, and on the host the owner of a
-// call's device buffers and the checks of a region's arguments (preprocess.hip and render.hip take those too).
+// What the post-processing's kernel files share (smooth.hip, compare.hip, consensus.hip, profile.hip, domains.hip, tracks.hip,
+// enrich.hip, enrich_null.hip, pileup.hip, query.hip): the capped grid, the wave helpers of their integer accumulations -- one
+// atomic per RUN of equal destination among consecutive lanes, because state maps are piecewise constant --, the split of a
+// label row into aligned words (tracks, enrich, enrich_null, query) and the tiles of a distance window (tracks; enrich and
+// enrich_null through enrich_tiles.h), the full-matrix area of a grid component, and on the host the owner of a call's device
+// buffers and the checks of a region's and a window's arguments (preprocess.hip and render.hip take those too).
 #pragma once
 
 #include "common.h"
+#include <climits>
 
 namespace phmrf {
 
@@ -44,6 +46,25 @@ __device__ __forceinline__ void wave_run_add(T* dst, int key, T x) {
   if (key >= 0 && next_head) atomicAdd(dst + key, x - (h > 0 ? before : (T)0));
 }
 
+// A lane's four keys after a 4-byte load: the run of equal key that starts them goes in through wave_run_add, the keys after
+// a change singly; key[e] < 0: the cell adds nothing.  Every lane of the wave must call it.  With x, cell e adds x[e], not 1.
+__device__ __forceinline__ void wave_quad_add(unsigned* dst, const int (&key)[4]) {
+  unsigned lead = key[0] >= 0 ? 1u : 0u;               // the lane's cells in the bin of its first
+  int e = 1;
+  for (; e < 4 && lead && key[e] == key[0]; ++e) ++lead;
+  wave_run_add(dst, key[0], lead);
+  for (; e < 4; ++e)
+    if (key[e] >= 0) atomicAdd(dst + key[e], 1u);
+}
+__device__ __forceinline__ void wave_quad_add(unsigned* dst, const int (&key)[4], const unsigned (&x)[4]) {
+  const bool r1 = key[0] >= 0 && key[1] == key[0], r2 = r1 && key[2] == key[0], r3 = r2 && key[3] == key[0];
+  const unsigned lead = (key[0] >= 0 ? x[0] : 0u) + (r1 ? x[1] : 0u) + (r2 ? x[2] : 0u) + (r3 ? x[3] : 0u);
+  wave_run_add(dst, key[0], lead);
+  if (!r1 && key[1] >= 0 && x[1]) atomicAdd(dst + key[1], x[1]);
+  if (!r2 && key[2] >= 0 && x[2]) atomicAdd(dst + key[2], x[2]);
+  if (!r3 && key[3] >= 0 && x[3]) atomicAdd(dst + key[3], x[3]);
+}
+
 // The stored cells of storage row i of a label map between the columns j0 and j1 (a diagonal block: from the diagonal on):
 // columns [ja, ja + nc) at p; `head` bytes (at most three) up to the next 4-byte boundary of the address, nvec aligned words of
 // four labels, then the bytes from `tail` on: nbytes = head + what follows the words.  A region's slice of a state_vec starts at
@@ -51,6 +72,8 @@ __device__ __forceinline__ void wave_run_add(T* dst, int key, T x) {
 struct LabelRow {
   const uint8_t* p;
   int ja, head, nvec, tail, nbytes;
+  // the cell, from p, of byte lane q < nbytes: the head bytes first, then the tail's
+  __device__ __forceinline__ int byte_at(int q) const { return q < head ? q : tail + (q - head); }
 };
 
 __device__ __forceinline__ LabelRow label_row(const uint8_t* __restrict__ labels, int i, int j0, int j1, int W, int diagonal) {
@@ -64,6 +87,12 @@ __device__ __forceinline__ LabelRow label_row(const uint8_t* __restrict__ labels
   r.tail = r.head + 4 * r.nvec;
   r.nbytes = r.head + (nc - r.tail);
   return r;
+}
+
+// lane q's loads of the row (the wave's lane, or the half-wave's where a half-wave holds a row); what it does not hold stays
+__device__ __forceinline__ void load_row(const LabelRow& r, int q, uint32_t* word, int* single) {
+  if (q < r.nvec) *word = *reinterpret_cast<const uint32_t*>(r.p + r.head + 4 * q);
+  if (q < r.nbytes) *single = r.p[r.byte_at(q)];
 }
 
 // band of a distance d >= 0: 0 for d == 0, else t with 2^(t-1) <= d < 2^t (PHMRF_DIFF_BANDS of them below 2^31)
@@ -129,6 +158,20 @@ __device__ __forceinline__ bool window_tile(int64_t T, int H, int W, int diagona
   return true;
 }
 
+// The rows i0 + first, + STEP, ... of tile t, one to an entry of word / single, as lane q of the lanes that hold a row reads
+// them: every load of the tile is issued before the first count.  An absent row, and what a lane does not hold of a row, is 0.
+template <int STEP, int N>
+__device__ __forceinline__ void load_tile_rows(const uint8_t* __restrict__ labels, const WindowTile& t, int W, int diagonal, int first,
+                                               int q, uint32_t (&word)[N], int (&single)[N]) {
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    const int i = t.i0 + first + STEP * u;
+    word[u] = 0;
+    single[u] = 0;                                     // (nc >= 1 below: a diagonal block's tile ends right of the diagonal)
+    if (i < t.i1) load_row(label_row(labels, i, t.j0, t.j1, W, diagonal), q, &word[u], &single[u]);
+  }
+}
+
 // ---- what the entry points share on the host ---------------------------------------------------------------------------
 
 // The device allocations of one call, freed on every way out.
@@ -182,6 +225,36 @@ inline int check_states(int K, int KB = 1, const char* names = "K") {
 inline int check_nodes(int64_t n, const char* msg = "the region must have fewer than 2^31 - 64 nodes") {
   PHMRF_CHECK(n < ((int64_t)1 << 31) - 64, PHMRF_ERR_UNSUPPORTED, msg);
   return PHMRF_OK;
+}
+
+inline int check_window(int64_t d_min, int64_t d_max) {
+  PHMRF_CHECK(d_min >= 0, PHMRF_ERR_INVALID, "d_min must be >= 0");
+  PHMRF_CHECK(d_max == -1 || d_max >= d_min, PHMRF_ERR_INVALID, "d_max must be >= d_min, or -1 for no upper limit");
+  return PHMRF_OK;
+}
+
+// an int holds dist0 + j - i of every cell of an H x W region and of a tile's padding (window_tile)
+inline int check_span(int64_t dist0, int H, int W) {
+  PHMRF_CHECK(dist0 > -((int64_t)1 << 31) && (dist0 < 0 ? -dist0 : dist0) + H + W < ((int64_t)1 << 31), PHMRF_ERR_UNSUPPORTED,
+              "|dist0| + H + W must be below 2^31");
+  return PHMRF_OK;
+}
+
+// the window for the kernels.  Every distance is below INT_MAX: a d_min up there leaves nothing inside, a d_max up there is none
+struct IntWindow {
+  int lo, hi;
+};
+inline IntWindow int_window(int64_t d_min, int64_t d_max) {
+  return IntWindow{d_min < INT_MAX ? (int)d_min : INT_MAX, (d_max == -1 || d_max > INT_MAX) ? INT_MAX : (int)d_max};
+}
+
+// the tiles window_tile<TILE_H, TILE_W> enumerates over an H x W region, and how many lie side by side
+template <int TILE_H, int TILE_W>
+inline int64_t window_tile_count(int H, int W, int diagonal, int* per_row) {
+  constexpr int PER_SUPER = TILE_W / TILE_H;
+  *per_row = (W + TILE_W - 1) / TILE_W;
+  return diagonal ? (int64_t)PER_SUPER * grid_row_first<int64_t>(*per_row, *per_row, 1)
+                  : (int64_t)((H + TILE_H - 1) / TILE_H) * *per_row;
 }
 
 // every distance |dist0 + j - i| of an H x W region is below 2^31 (band_of, the int distances of domains.hip)

@@ -22,8 +22,6 @@
 
 #include "runs.h"
 
-#include <climits>
-
 namespace phmrf {
 namespace {
 
@@ -32,7 +30,6 @@ constexpr int TRACKS_TILE_H = 32;        // storage rows of a tile (tracks.py TI
 constexpr int TRACKS_TILE_W = 256;       // storage columns of a tile: 64 lanes x 4 labels (tracks.py TILE_W)
 constexpr int TRACKS_STRIDE = 65;        // u32 words per tile row / column: 64 states and one word that keeps neighbours off one bank
 constexpr int TRACKS_ROWS_PER_WAVE = TRACKS_TILE_H / 4;          // a workgroup is four waves
-constexpr int TRACKS_PER_SUPER = TRACKS_TILE_W / TRACKS_TILE_H;   // tiles of a square super-tile (diagonal blocks)
 
 // table: u32 [(H + W) K], the rows' counts and then the columns' (a diagonal block: [H K]); d_hi: INT_MAX for no upper limit
 __global__ __launch_bounds__(256) void tracks_kernel(const uint8_t* __restrict__ labels, int H, int W, int diagonal, int dist0,
@@ -50,20 +47,9 @@ __global__ __launch_bounds__(256) void tracks_kernel(const uint8_t* __restrict__
   for (int64_t T = blockIdx.x; T < ntiles; T += gridDim.x) {
     WindowTile t;
     if (!window_tile<TRACKS_TILE_H, TRACKS_TILE_W>(T, H, W, diagonal, per_row, dist0, d_lo, d_hi, &t)) continue;
-    // the wave's rows i0 + wave, i0 + wave + 4, ...: every load of the tile is issued before the first count
     uint32_t word[TRACKS_ROWS_PER_WAVE];
     int single[TRACKS_ROWS_PER_WAVE];
-#pragma unroll
-    for (int u = 0; u < TRACKS_ROWS_PER_WAVE; ++u) {
-      const int i = t.i0 + wave + 4 * u;
-      word[u] = 0;
-      single[u] = 0;
-      if (i < t.i1) {                                                  // (everything but `lane` is the same for the wave)
-        const LabelRow r = label_row(labels, i, t.j0, t.j1, W, diagonal);   // (nc >= 1: a diagonal block's tile ends right of the diagonal)
-        if (lane < r.nvec) word[u] = *reinterpret_cast<const uint32_t*>(r.p + r.head + 4 * lane);
-        if (lane < r.nbytes) single[u] = r.p[lane < r.head ? lane : r.tail + (lane - r.head)];
-      }
-    }
+    load_tile_rows<4>(labels, t, W, diagonal, wave, lane, word, single);    // the wave's rows i0 + wave, i0 + wave + 4, ...
 #pragma unroll
     for (int u = 0; u < TRACKS_ROWS_PER_WAVE; ++u) {
       const int i = t.i0 + wave + 4 * u;
@@ -95,17 +81,12 @@ __global__ __launch_bounds__(256) void tracks_kernel(const uint8_t* __restrict__
             key[e] = s < 0 ? -1 : row_key + s;
           }
         }
-        unsigned lead = key[0] >= 0 ? 1u : 0u;          // the lane's cells in the state of its first
-        int e = 1;
-        for (; e < 4 && lead && key[e] == key[0]; ++e) ++lead;
-        wave_run_add(row_tab, key[0], lead);
-        for (; e < 4; ++e)
-          if (key[e] >= 0) atomicAdd(row_tab + key[e], 1u);
+        wave_quad_add(row_tab, key);
       }
       if (r.nbytes > 0) {
         int key = -1;
         if (lane < r.nbytes) {
-          const int s = cell(single[u], r.ja + (lane < r.head ? lane : r.tail + (lane - r.head)));
+          const int s = cell(single[u], r.ja + r.byte_at(lane));
           key = s < 0 ? -1 : row_key + s;
         }
         wave_run_add(row_tab, key, key >= 0 ? 1u : 0u);
@@ -144,25 +125,18 @@ extern "C" {
 int phmrf_state_tracks(const uint8_t* labels_dev, int H, int W, int diagonal, int64_t dist0, int K, int64_t d_min, int64_t d_max,
                        int64_t* rows_host, int64_t* cols_host_or_null, void* hip_stream) {
   PHMRF_CHECK(labels_dev && rows_host, PHMRF_ERR_INVALID, "NULL labels or rows");
-  PHMRF_CHECK(diagonal == 0 || diagonal == 1, PHMRF_ERR_INVALID, "diagonal must be 0 or 1");
+  int64_t n;
+  PHMRF_TRY(check_region(H, W, diagonal, &n));
   PHMRF_CHECK(diagonal || cols_host_or_null, PHMRF_ERR_INVALID, "an off-diagonal block needs cols");
-  PHMRF_CHECK(H >= 1 && W >= 1, PHMRF_ERR_INVALID, "H and W must be >= 1");
-  PHMRF_CHECK(K >= 1, PHMRF_ERR_INVALID, "K must be >= 1");
-  PHMRF_CHECK(!diagonal || H == W, PHMRF_ERR_INVALID, "a diagonal block is square (H == W)");
   PHMRF_CHECK(!diagonal || dist0 == 0, PHMRF_ERR_INVALID, "a diagonal block has dist0 == 0");
-  PHMRF_CHECK(d_min >= 0, PHMRF_ERR_INVALID, "d_min must be >= 0");
-  PHMRF_CHECK(d_max == -1 || d_max >= d_min, PHMRF_ERR_INVALID, "d_max must be >= d_min, or -1 for no upper limit");
-  PHMRF_CHECK(K <= 64, PHMRF_ERR_UNSUPPORTED, "K must be <= 64");
-  const int64_t n = grid_row_first<int64_t>(H, W, diagonal);
+  PHMRF_TRY(check_window(d_min, d_max));
+  PHMRF_TRY(check_states(K));
   PHMRF_TRY(check_nodes(n, "n must be below 2^31 - 64"));
-  PHMRF_CHECK(dist0 > -((int64_t)1 << 31) && dist0 < ((int64_t)1 << 31) &&
-                  (dist0 < 0 ? -dist0 : dist0) + H + W < ((int64_t)1 << 31),
-              PHMRF_ERR_UNSUPPORTED, "|dist0| + H + W must be below 2^31");
+  PHMRF_TRY(check_span(dist0, H, W));
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   const size_t words = ((size_t)H + (diagonal ? 0 : (size_t)W)) * (size_t)K;
-  const int per_row = (W + TRACKS_TILE_W - 1) / TRACKS_TILE_W;
-  const int64_t ntiles = diagonal ? (int64_t)TRACKS_PER_SUPER * grid_row_first<int64_t>(per_row, per_row, 1)
-                                  : (int64_t)((H + TRACKS_TILE_H - 1) / TRACKS_TILE_H) * per_row;
+  int per_row;
+  const int64_t ntiles = window_tile_count<TRACKS_TILE_H, TRACKS_TILE_W>(H, W, diagonal, &per_row);
 
   Buffers buf;
   unsigned* table;
@@ -171,10 +145,9 @@ int phmrf_state_tracks(const uint8_t* labels_dev, int H, int W, int diagonal, in
   PHMRF_TRY(buf.get(&flag, 1));
   PHMRF_HIP(hipMemsetAsync(table, 0, words * sizeof(unsigned), st));
   PHMRF_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
-  // every distance is below INT_MAX: a d_min up there leaves nothing inside, a d_max up there is no limit
-  const int d_lo = d_min < INT_MAX ? (int)d_min : INT_MAX, d_hi = (d_max == -1 || d_max > INT_MAX) ? INT_MAX : (int)d_max;
+  const IntWindow win = int_window(d_min, d_max);
   hipLaunchKernelGGL(tracks_kernel, dim3(grid_of(ntiles, 1, TRACKS_GRID_CAP)), dim3(256), 0, st, labels_dev, H, W, diagonal,
-                     (int)dist0, K, d_lo, d_hi, per_row, ntiles, table, flag);
+                     (int)dist0, K, win.lo, win.hi, per_row, ntiles, table, flag);
   PHMRF_HIP(hipGetLastError());
   int bad = 0;
   PHMRF_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));

@@ -282,10 +282,12 @@ def test_constants_are_the_headers_and_the_sources():
     assert "PHMRF_API int phmrf_pair_enrichment(" in txt
     assert len(_lib.SIGNATURES["phmrf_pair_enrichment"]) == 19
     src = open(os.path.join(ROOT, "phylo_hmrf_amd", "csrc", "enrich.hip")).read()
+    tiles = open(os.path.join(ROOT, "phylo_hmrf_amd", "csrc", "enrich_tiles.h")).read()      # the tile both kernels compile
     assert "ENRICH_GRID_CAP = %d;" % enrich.GRID_CAP in src
-    assert "ENRICH_TILE_H = %d;" % enrich.TILE_H in src
-    assert "ENRICH_TILE_W = %d;" % enrich.TILE_W in src
+    assert "ENRICH_TILE_H = %d;" % enrich.TILE_H in tiles and "ENRICH_TILE_H =" not in src
+    assert "ENRICH_TILE_W = %d;" % enrich.TILE_W in tiles and "ENRICH_TILE_W =" not in src
     assert "ENRICH_CHUNK = %d;" % enrich.CHUNK in src
-    assert "ENRICH_MAX_CLASSES = %d;" % enrich.MAX_CLASSES in src
-    assert '#include "runs.h"' in src
-    assert "enrich.hip" in open(os.path.join(ROOT, "phylo_hmrf_amd", "csrc", "Makefile")).read()
+    assert "ENRICH_MAX_CLASSES = %d;" % enrich.MAX_CLASSES in tiles and "ENRICH_MAX_CLASSES =" not in src
+    assert '#include "enrich_tiles.h"' in src and '#include "runs.h"' in tiles
+    mk = open(os.path.join(ROOT, "phylo_hmrf_amd", "csrc", "Makefile")).read()
+    assert "enrich.hip" in mk and "enrich_tiles.h" in mk

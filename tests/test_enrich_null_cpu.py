@@ -184,7 +184,9 @@ def test_null_group_is_the_sources_rule():
     src = open(os.path.join(ROOT, "phylo_hmrf_amd", "csrc", "enrich_null.hip")).read()
     for name in ("NULL_LDS_BYTES", "NULL_MAX_GROUP", "NULL_GRID_CAP", "NULL_CLASS_CAP", "NULL_CHUNK", "NULL_MAX_SHIFTS"):
         assert "%s = %d;" % (name, getattr(enrich, name)) in src, name
-    assert "NULL_TILE_H = %d;" % enrich.TILE_H in src and "NULL_TILE_W = %d;" % enrich.TILE_W in src
+    tiles = open(os.path.join(ROOT, "phylo_hmrf_amd", "csrc", "enrich_tiles.h")).read()      # enrich.hip's tile, compiled here too
+    assert "ENRICH_TILE_H = %d;" % enrich.TILE_H in tiles and "ENRICH_TILE_W = %d;" % enrich.TILE_W in tiles
+    assert "NULL_BINS = ENRICH_TILE_H + ENRICH_TILE_W;" in src and "TILE_H =" not in src and "TILE_W =" not in src
     assert "const int per = 4 * 2 * C * C * K + 8 * NULL_BINS;" in src and "NULL_LDS_BYTES / per" in src
     assert enrich.null_group(64, 8) == 1 and enrich.null_group(20, 3) == 16 and enrich.null_group(1, 1) == 16
     assert enrich.null_group(64, 4) == 6 and enrich.null_group(20, 8) == 5 and enrich.null_group(64, 3) == 11
@@ -192,7 +194,7 @@ def test_null_group_is_the_sources_rule():
         for C in (1, 2, 3, 8):
             ts = enrich.null_group(K, C)
             assert ts * (4 * 2 * C * C * K + 8 * (enrich.TILE_H + enrich.TILE_W)) <= 65536 and 1 <= ts <= 16
-    assert '#include "runs.h"' in src and "enrich_null.hip" in open(os.path.join(ROOT, "phylo_hmrf_amd", "csrc", "Makefile")).read()
+    assert '#include "enrich_tiles.h"' in src and '#include "runs.h"' in tiles and "enrich_null.hip" in open(os.path.join(ROOT, "phylo_hmrf_amd", "csrc", "Makefile")).read()
 
 
 def test_the_header_keeps_its_version_and_gains_one_entry_point():
