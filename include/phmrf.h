@@ -670,6 +670,42 @@ PHMRF_API int phmrf_rect_states(const uint8_t* labels_dev, const float* conf_dev
                                 int64_t Q, int64_t* counts_host /* [Q][K] */, int64_t* conf_host_or_null /* [Q] */,
                                 void* hip_stream);
 
+/* phmrf_state_aggregate: the rescaled pile-up of ONE CHROMOSOME's state map over features of unequal size (DESIGN.md section
+ * 7; no block, no ABI bump).  This is the one map call that takes every region of a chromosome at once and not one region:
+ * a feature's vote needs the histogram of a rectangle over every region that touches it.  labels_dev is the whole state_vec
+ * (n_labels bytes); region r is regions_host[r] = (lo, H, W, start_bin1, start_bin2, diagonal): its nodes are
+ * labels_dev[lo .. lo + n) in the node order of phmrf_smooth_labels, and its stored node (i, j) stands for the bin pair
+ * (p, q) = (start_bin1 + i, start_bin2 + j) of the chromosome.
+ * Feature f is feat_dev[f] = (a0, a1, b0, b1): the bin intervals A = [a0, a1) and B = [b0, b1), which may reach below bin 0
+ * and beyond the map; flip_dev_or_null[f] in {0, 1}.  The pile has P = T + 2 F cells per axis: a body of T cells and a flank
+ * of F cells on either side, which scales with the feature.  For an interval [x0, x1) of n bins
+ *   edge(c) = x0 + floor((c - F) n / T), c = 0 .. P (a true floor: the left flank's numerators are negative),
+ *   cell c  = the bins [edge(c), max(edge(c) + 1, edge(c + 1))):
+ * the body cells tile the interval exactly when n >= T, and repeat bins (nearest-neighbour upsampling) when n < T.  Pile cell
+ * (u, v) of feature f is I x J with I = cell u' of A and J = cell v' of B, (u', v') = (u, v), or (P - 1 - u, P - 1 - v) when
+ * the feature is flipped, and
+ *   hist[f][u][v][k]    = over the stored nodes (p, q) of all R regions in state k: [(p, q) in I x J] + [p != q and (q, p) in I x J]
+ * -- the symmetric chromosome matrix read through all its regions; regions that overlap count where they overlap once each.
+ *   group_offsets_host  host int64 [G + 1]: the features of group g are the entries [offsets[g], offsets[g + 1])
+ *   cells_host          host int64 [G][P][P][K], written in full: cells[g][u][v][k] = the sum of hist[f][u][v][k] over group g
+ *   votes_host          host int64 [G][P][P][K], written in full: votes[g][u][v][k] = the features f of group g with
+ *                       sum_k hist[f][u][v][k] > 0 whose largest hist[f][u][v][.] is at k, the lowest k on ties
+ * Features are not deduplicated.  A node in no cell of any feature is never inspected: a label >= K there is no error.  No
+ * features at all: zeros and PHMRF_OK, no launch.  Queued on hip_stream, returns when done.  Integers only: the same bytes
+ * from run to run, whatever PHMRF_DETERMINISTIC says.
+ * PHMRF_ERR_INVALID (nothing written) for a NULL labels_dev, regions_host, group_offsets_host or table, NULL features with
+ * features, n_labels < 1, R < 1, K < 1, T < 1, F < 0, G < 1, a region with H < 1, W < 1, a diagonal flag that is not 0 or 1, a
+ * non-square diagonal block, lo < 0, lo + n > n_labels or a negative start bin, offsets that do not start at 0 or that
+ * decrease, a flip > 1, a feature with a1 <= a0 or b1 <= b0, or a label >= K inside some feature's cell;
+ * PHMRF_ERR_UNSUPPORTED (nothing written) for K > 64, T > 64, F > 32, G > 16, R > 64, G P P K > 2^24, a region with
+ * n >= 2^31 - 64 or a start bin >= 2^30, 2^31 features or more, or a feature coordinate with |c| >= 2^30. */
+PHMRF_API int phmrf_state_aggregate(const uint8_t* labels_dev, int64_t n_labels, int R,
+                                    const int64_t* regions_host /* [R][6]: lo, H, W, start_bin1, start_bin2, diagonal */,
+                                    int K, int T, int F, int G, const int64_t* group_offsets_host /* [G+1] */,
+                                    const int32_t* feat_dev /* [N][4]: a0, a1, b0, b1 */,
+                                    const uint8_t* flip_dev_or_null /* NULL: all 0 */, int64_t* cells_host /* [G][P][P][K] */,
+                                    int64_t* votes_host /* [G][P][P][K] */, void* hip_stream);
+
 /* ---- profiling the states ------------------------------------------------------------------------- */
 /* What a state IS, from the block's resident f32 observations x (the uploaded float64 rounded to nearest) and its current
  * labels (no ABI bump: the calls only add entry points).  Both calls run over the nodes the block OWNS

@@ -198,6 +198,26 @@ def parse_args(argv=None):
     parser.add_option("--query_field", default="state_vec", help="--query: state_vec or state_vec_smooth")
     parser.add_option("--query_shift", default="0", help="--query: also count two controls per line, both intervals shifted by "
                       "this many bp (a whole number of bins) along the diagonal in either direction; 0: no controls")
+    parser.add_option("--aggregate", default="", help="skip loading data and fitting: the rescaled pile-up of this .mat over the "
+                      "intervals of --aggregate_bed (TAD or domain bodies) or the interval pairs of --aggregate_bedpe: every "
+                      "feature is stretched or shrunk onto a grid of --aggregate_body cells with --aggregate_flank cells on either "
+                      "side, and per grid cell the features vote with their dominant state; writes aggregate_<stem>.npz, "
+                      "aggregate_<stem>.txt and one aggregate_<stem>_<name>.png per name under --output (--resolution gives the "
+                      "bin size)")
+    parser.add_option("--aggregate_bed", default="", help="--aggregate: a BED file `chrom start stop [name [score [strand]]]` with at "
+                      "most 8 distinct names; an interval takes every bin it overlaps, strand - reverses the feature")
+    parser.add_option("--aggregate_bedpe", default="", help="--aggregate: a BEDPE file `chrom1 start1 stop1 chrom2 start2 stop2 "
+                      "[name]`, both ends on one chromosome")
+    parser.add_option("--aggregate_field", default="state_vec", help="--aggregate: state_vec or state_vec_smooth")
+    parser.add_option("--aggregate_body", default="32", help="--aggregate: the cells a feature's body is cut into, 1 .. 64")
+    parser.add_option("--aggregate_flank", default="16", help="--aggregate: the cells on either side of the body, 0 .. 32; a flank "
+                      "cell is as long as a body cell, so the flank scales with the feature")
+    parser.add_option("--aggregate_shift", default="0", help="--aggregate: also pile up controls, every feature shifted by this many "
+                      "bp (a whole number of bins) along the diagonal in either direction; 0: no controls")
+    parser.add_option("--aggregate_min", default="0", help="--aggregate: leave out features (for a BEDPE line: ends) shorter than "
+                      "this many bp")
+    parser.add_option("--aggregate_colors", default="", help="--aggregate: a text file of R G B rows (0 .. 255), one per state, in "
+                      "place of the built-in palette")
     parser.add_option("-h", "--help", action="help")
     opts, _ = parser.parse_args(argv)
     return opts
@@ -325,13 +345,14 @@ def check_ancestral(ancestral, segment, postprocess):
                          "its segmentation")
 
 
-def check_profile(profile, profile_quantiles, postprocess, compare, consensus="", query=""):
+def check_profile(profile, profile_quantiles, postprocess, compare, consensus="", query="", aggregate=""):
     """--profile 1 needs the observations on the GPU: it goes with a fit or --segment -> the quantiles, or None when off"""
     if str(profile) not in ("0", "1"):
         raise SystemExit("--profile must be 0 or 1")
     if str(profile) == "0":
         return None
-    for name, value in (("--postprocess", postprocess), ("--compare", compare), ("--consensus", consensus), ("--query", query)):
+    for name, value in (("--postprocess", postprocess), ("--compare", compare), ("--consensus", consensus), ("--query", query),
+                        ("--aggregate", aggregate)):
         if value:
             raise SystemExit("--profile 1 cannot be combined with %s, which loads no data: the profile needs the observations"
                              % name)
@@ -355,7 +376,7 @@ def write_profile(model, state_vec, quantiles, output_path, run_id, K, species, 
 
 
 def check_compare(compare, compare_with, compare_field, compare_match, segment, postprocess, ancestral, save_model,
-                  filter_device, consensus="", query=""):
+                  filter_device, consensus="", query="", aggregate=""):
     """--compare A.mat --compare_with B.mat reads two finished state maps: it goes with nothing that loads data or fits"""
     if not compare and not compare_with:
         return
@@ -363,7 +384,8 @@ def check_compare(compare, compare_with, compare_field, compare_match, segment, 
         raise SystemExit("--compare and --compare_with go together: the two .mat files to compare")
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--ancestral", ancestral),
                         ("--save_model", save_model), ("--filter_device 1", str(filter_device) == "1"),
-                        ("--consensus", consensus), ("--query", query)):
+                        ("--consensus", consensus), ("--query", query),
+                        ("--aggregate", aggregate)):
         if value:
             raise SystemExit("--compare cannot be combined with %s: it loads no data and fits nothing" % name)
     if compare_field not in ("state_vec", "state_vec_smooth"):
@@ -373,13 +395,14 @@ def check_compare(compare, compare_with, compare_field, compare_match, segment, 
 
 
 def check_domains(domains, domains_field, segment, postprocess, compare, ancestral, save_model, profile, filter_device,
-                  consensus="", query=""):
+                  consensus="", query="", aggregate=""):
     """--domains FILE.mat reads one finished state map: it goes with nothing that loads data or fits"""
     if not domains:
         return
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare),
                         ("--ancestral", ancestral), ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
-                        ("--filter_device 1", str(filter_device) == "1"), ("--consensus", consensus), ("--query", query)):
+                        ("--filter_device 1", str(filter_device) == "1"), ("--consensus", consensus), ("--query", query),
+                        ("--aggregate", aggregate)):
         if value:
             raise SystemExit("--domains cannot be combined with %s: it loads no data and fits nothing" % name)
     if domains_field not in ("state_vec", "state_vec_smooth"):
@@ -387,13 +410,14 @@ def check_domains(domains, domains_field, segment, postprocess, compare, ancestr
 
 
 def check_render(render, render_field, render_side, render_outline, render_conf, segment, postprocess, compare, domains,
-                 ancestral, save_model, profile, filter_device, consensus="", query=""):
+                 ancestral, save_model, profile, filter_device, consensus="", query="", aggregate=""):
     """--render FILE.mat reads one finished state map: it goes with nothing that loads data or fits -> the side, or None"""
     if not render:
         return None
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
                         ("--ancestral", ancestral), ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
-                        ("--filter_device 1", str(filter_device) == "1"), ("--consensus", consensus), ("--query", query)):
+                        ("--filter_device 1", str(filter_device) == "1"), ("--consensus", consensus), ("--query", query),
+                        ("--aggregate", aggregate)):
         if value:
             raise SystemExit("--render cannot be combined with %s: it loads no data and fits nothing" % name)
     if render_field not in ("state_vec", "state_vec_smooth"):
@@ -411,7 +435,7 @@ def check_render(render, render_field, render_side, render_outline, render_conf,
 
 
 def check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment, postprocess, compare, domains, ancestral,
-                 save_model, profile, filter_device, consensus="", query=""):
+                 save_model, profile, filter_device, consensus="", query="", aggregate=""):
     """--tracks FILE.mat reads one finished state map: it goes with nothing that loads data or fits -> the windows in bins,
     or None"""
     if not tracks:
@@ -419,7 +443,8 @@ def check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment,
     for name, value in (("--render", render), ("--segment", segment), ("--postprocess", postprocess), ("--compare", compare),
                         ("--domains", domains), ("--ancestral", ancestral), ("--save_model", save_model),
                         ("--profile 1", str(profile) == "1"), ("--filter_device 1", str(filter_device) == "1"),
-                        ("--consensus", consensus), ("--query", query)):
+                        ("--consensus", consensus), ("--query", query),
+                        ("--aggregate", aggregate)):
         if value:
             raise SystemExit("--tracks cannot be combined with %s: it loads no data and fits nothing" % name)
     if tracks_field not in ("state_vec", "state_vec_smooth"):
@@ -432,7 +457,7 @@ def check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment,
 
 
 def check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments, resolution, segment, postprocess, compare,
-                 domains, render, tracks, ancestral, save_model, profile, filter_device, consensus="", query=""):
+                 domains, render, tracks, ancestral, save_model, profile, filter_device, consensus="", query="", aggregate=""):
     """--enrich FILE.mat --enrich_bed FILE reads one finished state map and an annotation: it goes with nothing that loads data
     or fits, and with no other reader of a state map -> the window (d_min, d_max) in bins, or None"""
     if not enrich:
@@ -444,7 +469,8 @@ def check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments,
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
                         ("--render", render), ("--tracks", tracks), ("--ancestral", ancestral), ("--save_model", save_model),
                         ("--profile 1", str(profile) == "1"), ("--filter_device 1", str(filter_device) == "1"),
-                        ("--consensus", consensus), ("--query", query)):
+                        ("--consensus", consensus), ("--query", query),
+                        ("--aggregate", aggregate)):
         if value:
             raise SystemExit("--enrich cannot be combined with %s: it loads no data and fits nothing" % name)
     if enrich_field not in ("state_vec", "state_vec_smooth"):
@@ -482,7 +508,7 @@ def check_enrich_null(enrich, enrich_null="0", enrich_null_min="1000000", enrich
 
 
 def check_pileup(pileup, pileup_bed, pileup_bedpe, pileup_field, pileup_flank, pileup_shift, resolution, segment, postprocess,
-                 compare, domains, render, tracks, enrich, ancestral, save_model, profile, filter_device, consensus="", query=""):
+                 compare, domains, render, tracks, enrich, ancestral, save_model, profile, filter_device, consensus="", query="", aggregate=""):
     """--pileup FILE.mat with --pileup_bed FILE or --pileup_bedpe FILE reads one finished state map and a list of anchors: it
     goes with nothing that loads data or fits, and with no other reader of a state map -> (the flank, the shift) in bins, or
     None"""
@@ -495,7 +521,8 @@ def check_pileup(pileup, pileup_bed, pileup_bedpe, pileup_field, pileup_flank, p
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
                         ("--render", render), ("--tracks", tracks), ("--enrich", enrich), ("--ancestral", ancestral),
                         ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
-                        ("--filter_device 1", str(filter_device) == "1"), ("--consensus", consensus), ("--query", query)):
+                        ("--filter_device 1", str(filter_device) == "1"), ("--consensus", consensus), ("--query", query),
+                        ("--aggregate", aggregate)):
         if value:
             raise SystemExit("--pileup cannot be combined with %s: it loads no data and fits nothing" % name)
     if pileup_field not in ("state_vec", "state_vec_smooth"):
@@ -508,7 +535,7 @@ def check_pileup(pileup, pileup_bed, pileup_bedpe, pileup_field, pileup_flank, p
 
 
 def check_consensus(consensus, consensus_field, consensus_match, consensus_support, consensus_area, segment, postprocess,
-                    compare, domains, render, tracks, enrich, pileup, ancestral, save_model, profile, filter_device, query=""):
+                    compare, domains, render, tracks, enrich, pileup, ancestral, save_model, profile, filter_device, query="", aggregate=""):
     """--consensus A.mat,B.mat,... reads finished state maps of the same regions: it goes with nothing that loads data or
     fits, and with no other reader of a state map -> (the files, min_support or None, min_area or None), or None"""
     if not consensus:
@@ -516,7 +543,8 @@ def check_consensus(consensus, consensus_field, consensus_match, consensus_suppo
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
                         ("--render", render), ("--tracks", tracks), ("--enrich", enrich), ("--pileup", pileup),
                         ("--ancestral", ancestral), ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
-                        ("--filter_device 1", str(filter_device) == "1"), ("--query", query)):
+                        ("--filter_device 1", str(filter_device) == "1"), ("--query", query),
+                        ("--aggregate", aggregate)):
         if value:
             raise SystemExit("--consensus cannot be combined with %s: it loads no data and fits nothing" % name)
     from phylo_hmrf_amd.consensus import CONSENSUS_MAPS
@@ -540,7 +568,7 @@ def check_consensus(consensus, consensus_field, consensus_match, consensus_suppo
 
 
 def check_query(query, query_bed, query_bedpe, query_field, query_shift, resolution, segment, postprocess, compare, domains,
-                render, tracks, enrich, pileup, consensus, ancestral, save_model, profile, filter_device):
+                render, tracks, enrich, pileup, consensus, ancestral, save_model, profile, filter_device, aggregate=""):
     """--query FILE.mat with --query_bed FILE or --query_bedpe FILE reads one finished state map and a list of intervals: it
     goes with nothing that loads data or fits, and with no other reader of a state map -> the shift in bins, or None"""
     if not query:
@@ -552,7 +580,8 @@ def check_query(query, query_bed, query_bedpe, query_field, query_shift, resolut
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
                         ("--render", render), ("--tracks", tracks), ("--enrich", enrich), ("--pileup", pileup),
                         ("--consensus", consensus), ("--ancestral", ancestral), ("--save_model", save_model),
-                        ("--profile 1", str(profile) == "1"), ("--filter_device 1", str(filter_device) == "1")):
+                        ("--profile 1", str(profile) == "1"), ("--filter_device 1", str(filter_device) == "1"),
+                        ("--aggregate", aggregate)):
         if value:
             raise SystemExit("--query cannot be combined with %s: it loads no data and fits nothing" % name)
     if query_field not in ("state_vec", "state_vec_smooth"):
@@ -562,6 +591,48 @@ def check_query(query, query_bed, query_bedpe, query_field, query_shift, resolut
         return check_bins(int(resolution), 0, int(query_shift))[1]
     except ValueError as e:
         raise SystemExit("--query with --query_shift %s: %s" % (query_shift, e))
+
+
+def check_aggregate(aggregate, aggregate_bed, aggregate_bedpe, aggregate_field, aggregate_body, aggregate_flank, aggregate_shift,
+                    aggregate_min, aggregate_colors, resolution, segment, postprocess, compare, domains, render, tracks, enrich,
+                    pileup, consensus, query, ancestral, save_model, profile, filter_device):
+    """--aggregate FILE.mat with --aggregate_bed FILE or --aggregate_bedpe FILE reads one finished state map and a list of
+    features: it goes with nothing that loads data or fits, and with no other reader of a state map -> (the body, the flank
+    in cells, the shift in bins, the shortest feature in bp), or None"""
+    if not aggregate:
+        if aggregate_bed or aggregate_bedpe:
+            raise SystemExit("--aggregate_bed and --aggregate_bedpe go with --aggregate: the .mat to pile up")
+        if (aggregate_field, str(aggregate_body), str(aggregate_flank), str(aggregate_shift), str(aggregate_min),
+                aggregate_colors) != ("state_vec", "32", "16", "0", "0", ""):
+            raise SystemExit("--aggregate_field, --aggregate_body, --aggregate_flank, --aggregate_shift, --aggregate_min and "
+                             "--aggregate_colors go with --aggregate")
+        return None
+    if bool(aggregate_bed) == bool(aggregate_bedpe):
+        raise SystemExit("--aggregate takes its features from --aggregate_bed or from --aggregate_bedpe: exactly one of the two")
+    for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
+                        ("--render", render), ("--tracks", tracks), ("--enrich", enrich), ("--pileup", pileup),
+                        ("--consensus", consensus), ("--query", query), ("--ancestral", ancestral), ("--save_model", save_model),
+                        ("--profile 1", str(profile) == "1"), ("--filter_device 1", str(filter_device) == "1")):
+        if value:
+            raise SystemExit("--aggregate cannot be combined with %s: it loads no data and fits nothing" % name)
+    if aggregate_field not in ("state_vec", "state_vec_smooth"):
+        raise SystemExit("--aggregate_field must be state_vec or state_vec_smooth, not %r" % (aggregate_field,))
+    from phylo_hmrf_amd.aggregate import MAX_BODY, MAX_FLANK
+    from phylo_hmrf_amd.pileup import check_bins
+    try:
+        body, flank, min_bp = int(aggregate_body), int(aggregate_flank), int(aggregate_min)
+    except ValueError:
+        raise SystemExit("--aggregate_body, --aggregate_flank and --aggregate_min must be integers")
+    if not 1 <= body <= MAX_BODY:
+        raise SystemExit("--aggregate_body must lie in 1 .. %d cells, not %d" % (MAX_BODY, body))
+    if not 0 <= flank <= MAX_FLANK:
+        raise SystemExit("--aggregate_flank must lie in 0 .. %d cells, not %d" % (MAX_FLANK, flank))
+    if min_bp < 0:
+        raise SystemExit("--aggregate_min must be >= 0 bp, not %d" % min_bp)
+    try:
+        return body, flank, check_bins(int(resolution), 0, int(aggregate_shift))[1], min_bp
+    except ValueError as e:
+        raise SystemExit("--aggregate with --aggregate_shift %s: %s" % (aggregate_shift, e))
 
 
 def run(num_states, chromvec, root_path, multiple, species_name, sort_states, run_id1, cons_param, method_mode,
@@ -578,29 +649,35 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
         pileup="", pileup_bed="", pileup_bedpe="", pileup_field="state_vec", pileup_flank="1000000", pileup_shift="0",
         pileup_colors="", consensus="", consensus_field="state_vec", consensus_match="0", consensus_support="-1",
         consensus_area="-1", query="", query_bed="", query_bedpe="", query_field="state_vec", query_shift="0",
-        enrich_null="0", enrich_null_min="1000000", enrich_null_seed="0"):
+        enrich_null="0", enrich_null_min="1000000", enrich_null_seed="0", aggregate="", aggregate_bed="", aggregate_bedpe="",
+        aggregate_field="state_vec", aggregate_body="32", aggregate_flank="16", aggregate_shift="0", aggregate_min="0",
+        aggregate_colors=""):
+    grid = check_aggregate(aggregate, aggregate_bed, aggregate_bedpe, aggregate_field, aggregate_body, aggregate_flank,
+                           aggregate_shift, aggregate_min, aggregate_colors, resolution, segment, postprocess,
+                           compare or compare_with, domains, render, tracks, enrich, pileup, consensus, query, ancestral,
+                           save_model, profile, filter_device)
     check_query(query, query_bed, query_bedpe, query_field, query_shift, resolution, segment, postprocess,
                 compare or compare_with, domains, render, tracks, enrich, pileup, consensus, ancestral, save_model, profile,
-                filter_device)
+                filter_device, aggregate=aggregate)
     vote = check_consensus(consensus, consensus_field, consensus_match, consensus_support, consensus_area, segment, postprocess,
                            compare or compare_with, domains, render, tracks, enrich, pileup, ancestral, save_model, profile,
-                           filter_device, query=query)
+                           filter_device, query=query, aggregate=aggregate)
     check_pileup(pileup, pileup_bed, pileup_bedpe, pileup_field, pileup_flank, pileup_shift, resolution, segment, postprocess,
                  compare or compare_with, domains, render, tracks, enrich, ancestral, save_model, profile, filter_device,
-                 consensus=consensus, query=query)
+                 consensus=consensus, query=query, aggregate=aggregate)
     check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments, resolution, segment, postprocess,
                  compare or compare_with, domains, render, tracks, ancestral, save_model, profile, filter_device,
-                 consensus=consensus, query=query)
+                 consensus=consensus, query=query, aggregate=aggregate)
     null = check_enrich_null(enrich, enrich_null, enrich_null_min, enrich_null_seed, resolution)
     check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment, postprocess, compare or compare_with, domains,
-                 ancestral, save_model, profile, filter_device, consensus=consensus, query=query)
+                 ancestral, save_model, profile, filter_device, consensus=consensus, query=query, aggregate=aggregate)
     side = check_render(render, render_field, render_side, render_outline, render_conf, segment, postprocess,
-                        compare or compare_with, domains, ancestral, save_model, profile, filter_device, consensus=consensus, query=query)
+                        compare or compare_with, domains, ancestral, save_model, profile, filter_device, consensus=consensus, query=query, aggregate=aggregate)
     check_domains(domains, domains_field, segment, postprocess, compare or compare_with, ancestral, save_model, profile,
-                  filter_device, consensus=consensus, query=query)
-    profile_q = check_profile(profile, profile_quantiles, postprocess, compare, consensus=consensus, query=query)
+                  filter_device, consensus=consensus, query=query, aggregate=aggregate)
+    profile_q = check_profile(profile, profile_quantiles, postprocess, compare, consensus=consensus, query=query, aggregate=aggregate)
     check_compare(compare, compare_with, compare_field, compare_match, segment, postprocess, ancestral, save_model,
-                  filter_device, consensus=consensus, query=query)
+                  filter_device, consensus=consensus, query=query, aggregate=aggregate)
     check_ancestral(ancestral, segment, postprocess)
     filter_device = int(filter_device)
     if filter_device not in (0, 1):
@@ -614,6 +691,13 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
         out = consensus_files(files, str(output_path), int(resolution), field=consensus_field, match=bool(int(consensus_match)),
                               min_support=support, min_area=area)
         print("consensus written: %s" % out)
+        return out
+    if aggregate:
+        from phylo_hmrf_amd.aggregate import aggregate_files
+        out = aggregate_files(aggregate, str(output_path), int(resolution), field=aggregate_field, bed=aggregate_bed,
+                              bedpe=aggregate_bedpe, body=grid[0], flank=grid[1], shift_bp=int(aggregate_shift), min_bp=grid[3],
+                              palette_path=aggregate_colors)
+        print("aggregate written: %s" % out)
         return out
     if query:
         from phylo_hmrf_amd.query import query_files
@@ -853,4 +937,7 @@ if __name__ == "__main__":
         consensus_match=opts.consensus_match, consensus_support=opts.consensus_support, consensus_area=opts.consensus_area,
         query=opts.query, query_bed=opts.query_bed, query_bedpe=opts.query_bedpe, query_field=opts.query_field,
         query_shift=opts.query_shift, enrich_null=opts.enrich_null, enrich_null_min=opts.enrich_null_min,
-        enrich_null_seed=opts.enrich_null_seed)
+        enrich_null_seed=opts.enrich_null_seed, aggregate=opts.aggregate, aggregate_bed=opts.aggregate_bed,
+        aggregate_bedpe=opts.aggregate_bedpe, aggregate_field=opts.aggregate_field, aggregate_body=opts.aggregate_body,
+        aggregate_flank=opts.aggregate_flank, aggregate_shift=opts.aggregate_shift, aggregate_min=opts.aggregate_min,
+        aggregate_colors=opts.aggregate_colors)
