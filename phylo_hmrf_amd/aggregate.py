@@ -29,13 +29,14 @@ len_vec rows: [n, start, stop, H, W, start_bin1, start_bin2, region_id, type (1 
 """
 import ctypes
 import os
-import re
 
 import numpy as np
 
-from .maps import MAX_STATES, annotation_lines, check_len_vec, check_resolution, check_state_vec, chrom_of, device, is_number, load_map, stem
-from .pileup import MAX_NAMES, check_bins, log2_ratio, pile_image, pile_summary
-from .render import default_palette, load_palette, write_png
+from .intervals import (MAX_GROUPS, MAX_NAMES, check_G, check_shift, held_chrom, held_chroms, interval_lines, log2_ratio, name_group,
+                        overlap_bins, pile_summary, shift_along_diagonal, summary_fields, write_group_images)
+from .maps import check_K, check_len_vec, check_resolution, check_state_vec, device, load_map, stem
+from .pileup import pile_image
+from .render import default_palette, load_palette
 
 LANES = 128                      # csrc/aggregate.hip AGG_LANES: pile cells of a tile = lanes of a workgroup of the lane kernel
 CHUNK = 256                      # csrc/aggregate.hip AGG_CHUNK: features of one group a workgroup piles at a time
@@ -46,10 +47,9 @@ WAVES = 4                        # csrc/aggregate.hip AGG_WAVES: waves of a work
 WAVE_GRID_CAP = 2048             # csrc/aggregate.hip AGG_WAVE_GRID_CAP: workgroups of the wave kernel
 MAX_BODY = 64                    # csrc/aggregate.hip AGG_MAX_BODY: T <= 64
 MAX_FLANK = 32                   # csrc/aggregate.hip AGG_MAX_FLANK: F <= 32
-MAX_GROUPS = 16                  # csrc/aggregate.hip AGG_MAX_GROUPS: 8 names and their 8 controls
 MAX_REGIONS = 64                 # csrc/aggregate.hip AGG_MAX_REGIONS: regions of one chromosome
 MAX_TABLE = 1 << 24              # csrc/aggregate.hip AGG_MAX_TABLE: G P P K entries of either table
-COORD_LIMIT = 1 << 30            # csrc/aggregate.hip AGG_COORD_LIMIT: |c| of a feature's coordinate stays below it
+COORD_LIMIT = 1 << 30            # csrc/interval_lists.h COORD_LIMIT: |c| of a feature's coordinate stays below it
 
 
 def _check_features(features):
@@ -111,12 +111,8 @@ def state_aggregate(state_vec, len_vec, features, body, flank, K=None, G=None):
     L = check_len_vec(len_vec, s.shape[0])
     T, F = _check_grid(body, flank)
     f = _check_features(features)
-    K = (int(s.max()) + 1 if s.size else 1) if K is None else int(K)
-    if K < 1 or K > MAX_STATES:
-        raise ValueError("K must be in 1 .. %d" % MAX_STATES)
-    G = (int(f[:, 5].max()) + 1 if f.shape[0] else 1) if G is None else int(G)
-    if G < 1 or G > MAX_GROUPS:
-        raise ValueError("G must be in 1 .. %d" % MAX_GROUPS)
+    K = check_K(s, K)
+    G = check_G(f[:, 5], G)
     if f.shape[0] and f[:, 5].max() >= G:
         raise ValueError("a feature's group must be below G = %d" % G)
     P = T + 2 * F
@@ -152,25 +148,6 @@ def state_aggregate(state_vec, len_vec, features, body, flank, K=None, G=None):
 
 
 # ---- the feature files ------------------------------------------------------------------------------------------------------
-def _bins(path, number, start, stop, res):
-    """-> (a0, a1, bp): the bins [a0, a1) that [start, stop) bp overlaps, at least one (query's BIN RULE), and its length"""
-    start, stop = int(start), int(stop)
-    if start < 0 or stop < 0:
-        raise ValueError("%s line %d: negative coordinate" % (path, number))
-    if stop < start:
-        raise ValueError("%s line %d: stop %d < start %d" % (path, number, stop, start))
-    a0 = start // res
-    return a0, max(a0 + 1, -(-stop // res)), stop - start
-
-
-def _group(path, number, names, name):
-    if name not in names:
-        if len(names) == MAX_NAMES:
-            raise ValueError("%s line %d: more than %d names (%s, then %r)" % (path, number, MAX_NAMES, ", ".join(names), name))
-        names.append(name)
-    return names.index(name)
-
-
 def _read(rows, names, skipped, short):
     return dict(features=np.array(rows, dtype=np.int64).reshape(-1, 7), names=names, skipped_lines=skipped, skipped_short=short)
 
@@ -187,21 +164,18 @@ def read_features(path, len_vec, resolution, min_bp=0):
     chrom is chr<N> or <N>, N the integer in len_vec's column 9.  Strand - sets flip (the pile is read against the genome's
     direction); +, . and no strand do not.  The names are numbered over the whole file.  ValueError for a malformed line,
     stop < start, a negative coordinate, any other strand and a ninth name.  Host only."""
-    res, min_bp = check_resolution(resolution), int(min_bp)
-    held = set(int(c) for c in np.unique(np.asarray(len_vec)[:, 9]))
+    res, min_bp, held = check_resolution(resolution), int(min_bp), held_chroms(len_vec)
     rows, names, skipped, short = [], [], 0, 0
-    for number, line, f in annotation_lines(path):
-        if len(f) < 3 or not is_number(f[1]) or not is_number(f[2]):
-            raise ValueError("%s line %d: expected `chrom start stop [name [score [strand]]]`, got %r" % (path, number, line))
-        a0, a1, bp = _bins(path, number, f[1], f[2], res)
-        strand = f[5] if len(f) > 5 else "."
+    for number, _, chroms, ((start, stop),), rest in interval_lines(path, 1, "chrom start stop [name [score [strand]]]", True):
+        a0, a1 = overlap_bins(start, stop, res)
+        strand = rest[2] if len(rest) > 2 else "."
         if strand not in ("+", "-", "."):
             raise ValueError("%s line %d: strand %r is not +, - or ." % (path, number, strand))
-        g = _group(path, number, names, f[3] if len(f) > 3 else "feature")
-        c = chrom_of(f[0])
-        if c not in held:
+        g = name_group(path, number, names, rest[0] if rest else "feature")
+        c = held_chrom(chroms, held)
+        if c is None:
             skipped += 1
-        elif bp < min_bp:
+        elif stop - start < min_bp:
             short += 1
         else:
             rows.append([c, a0, a1, a0, a1, g, 1 if strand == "-" else 0])
@@ -213,19 +187,15 @@ def read_feature_pairs(path, len_vec, resolution, min_bp=0):
     b0, b1, group, 0: A and B the bins the two intervals overlap, swapped so that a0 <= b0 (the pile's u axis is the end
     nearer the chromosome's start, as in --pileup).  A line whose two ends are not on one chromosome of len_vec is skipped
     and counted, a line with an end shorter than min_bp too; a line without a name is named `pair`.  Host only."""
-    res, min_bp = check_resolution(resolution), int(min_bp)
-    held = set(int(c) for c in np.unique(np.asarray(len_vec)[:, 9]))
+    res, min_bp, held = check_resolution(resolution), int(min_bp), held_chroms(len_vec)
     rows, names, skipped, short = [], [], 0, 0
-    for number, line, f in annotation_lines(path):
-        if len(f) < 6 or not all(is_number(f[t]) for t in (1, 2, 4, 5)):
-            raise ValueError("%s line %d: expected `chrom1 start1 stop1 chrom2 start2 stop2 [name]`, got %r" % (path, number, line))
-        a0, a1, bp_a = _bins(path, number, f[1], f[2], res)
-        b0, b1, bp_b = _bins(path, number, f[4], f[5], res)
-        g = _group(path, number, names, f[6] if len(f) > 6 else "pair")
-        c = chrom_of(f[0])
-        if c not in held or chrom_of(f[3]) != c:
+    for number, _, chroms, spans, rest in interval_lines(path, 2, "chrom1 start1 stop1 chrom2 start2 stop2 [name]", True):
+        (a0, a1), (b0, b1) = (overlap_bins(start, stop, res) for start, stop in spans)
+        g = name_group(path, number, names, rest[0] if rest else "pair")
+        c = held_chrom(chroms, held)
+        if c is None:
             skipped += 1
-        elif min(bp_a, bp_b) < min_bp:
+        elif min(stop - start for start, stop in spans) < min_bp:
             short += 1
         else:
             rows.append([c] + ([a0, a1, b0, b1] if a0 <= b0 else [b0, b1, a0, a1]) + [g, 0])
@@ -237,17 +207,12 @@ def with_controls(features, shift_bins, G):
     ALONG the diagonal (both intervals move together, so every bin pair keeps its genomic distance: query.with_controls'
     rule) as group G + g with the same flip.  A control with a negative bin is dropped.  Host only."""
     f = _check_features(features)
-    shift, G = int(shift_bins), int(G)
-    if shift < 1:
-        raise ValueError("shift_bins must be >= 1")
+    ctl, keep = shift_along_diagonal(f, ((1, 2), (3, 4)), shift_bins)
+    G = int(G)
     if G < 1 or (f.shape[0] and f[:, 5].max() >= G):
         raise ValueError("G must be >= 1 and above every feature's group")
-    both = np.stack([f, f], axis=1)                           # per feature: the control before it, the control after it
-    both[:, 0, 1:5] -= shift
-    both[:, 1, 1:5] += shift
-    both[:, :, 5] += G
-    ctl = both.reshape(-1, 7)
-    return np.concatenate([f, ctl[(ctl[:, 1] >= 0) & (ctl[:, 3] >= 0)]])
+    ctl[:, 5] += G
+    return np.concatenate([f, ctl[keep]])
 
 
 # ---- reading and writing a pile ---------------------------------------------------------------------------------------------
@@ -259,22 +224,15 @@ def aggregate_lines(votes, cells, names, body, flank, ctl_votes=None):
     o, c = np.asarray(votes), np.asarray(cells)
     G, P, _, K = o.shape
     T, F = int(body), int(flank)
-    sm = pile_summary(o)
     pairs = c.sum(axis=-1)
-    head = ["#name", "u", "v", "u_pos", "v_pos", "features", "dominant_state", "share", "entropy_bits", "bin_pairs"]
-    if ctl_votes is not None:
-        head += ["control_features", "log2_ratio"]
-        ctl_total, l2 = np.asarray(ctl_votes).sum(axis=-1), log2_ratio(o, ctl_votes)
-    lines = ["\t".join(head + ["state_%d" % (k + 1) for k in range(K)]) + "\n"]
+    (core_head, tail_head), fields = summary_fields(o, ctl_votes, "control_features")
+    lines = ["\t".join(["#name", "u", "v", "u_pos", "v_pos", "features"] + core_head + ["bin_pairs"] + tail_head) + "\n"]
     for g in range(G):
         for a in range(P):
             for b in range(P):
-                dom = int(sm["dominant"][g, a, b])
-                f = [names[g], "%d" % a, "%d" % b, "%.4f" % ((a - F + 0.5) / T), "%.4f" % ((b - F + 0.5) / T), "%d" % sm["total"][g, a, b],
-                     "%d" % (dom + 1), "%.6f" % sm["share"][g, a, b], "%.6f" % sm["entropy"][g, a, b], "%d" % pairs[g, a, b]]
-                if ctl_votes is not None:
-                    f += ["%d" % ctl_total[g, a, b], "%.4f" % (l2[g, a, b, dom] if dom >= 0 else np.nan)]
-                lines.append("\t".join(f + ["%d" % x for x in o[g, a, b]]) + "\n")
+                core, tail = fields((g, a, b))
+                f = [names[g], "%d" % a, "%d" % b, "%.4f" % ((a - F + 0.5) / T), "%.4f" % ((b - F + 0.5) / T)]
+                lines.append("\t".join(f + core + ["%d" % pairs[g, a, b]] + tail) + "\n")
     return lines
 
 
@@ -291,7 +249,7 @@ def aggregate_files(path, output_path, resolution, field="state_vec", bed="", be
     if bool(bed) == bool(bedpe):
         raise ValueError("aggregate_files takes a bed file or a bedpe file, one of the two")
     T, F = _check_grid(body, flank)
-    shift = check_bins(res, 0, shift_bp)[1]
+    shift = check_shift(res, shift_bp)
     if int(min_bp) < 0:
         raise ValueError("min_bp must be >= 0")
     s, L, _ = load_map(path, field)
@@ -316,11 +274,5 @@ def aggregate_files(path, output_path, resolution, field="state_vec", bed="", be
              feature_kind=np.array("bed" if bed else "bedpe"), shift_bp=np.int64(shift_bp), min_bp=np.int64(min_bp), **extra)
     with open(os.path.join(output_path, "aggregate_%s.txt" % name), "wb") as fh:
         fh.write("".join(aggregate_lines(votes, cells, names, T, F, ctl_votes)).encode())
-    used = set()
-    for g, group in enumerate(names):
-        safe = re.sub(r"[^A-Za-z0-9._-]", "_", group)
-        if safe in used:
-            safe = "%s_g%d" % (safe, g)
-        used.add(safe)
-        write_png(os.path.join(output_path, "aggregate_%s_%s.png" % (name, safe)), pile_image(votes[g], palette))
+    write_group_images(output_path, "aggregate_%s" % name, names, [pile_image(votes[g], palette) for g in range(G)])
     return out

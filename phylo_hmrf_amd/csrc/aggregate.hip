@@ -31,7 +31,7 @@
 //   A feature whose window misses every region, and a cell whose rectangle misses a region, cost no label load.
 //   Flag bits: a label >= K inside a cell, a flip > 1, a coordinate with |c| >= 2^30, an empty interval.
 
-#include "runs.h"
+#include "interval_lists.h"
 
 namespace phmrf {
 namespace {
@@ -45,10 +45,8 @@ constexpr int AGG_WAVE_GRID_CAP = 2048;  // workgroups of the wave kernel (aggre
 constexpr int AGG_ROW_W = 256;           // columns of a row piece: at most one 4-byte word a lane
 constexpr int AGG_MAX_BODY = 64;         // T <= 64 (aggregate.py MAX_BODY)
 constexpr int AGG_MAX_FLANK = 32;        // F <= 32 (aggregate.py MAX_FLANK)
-constexpr int AGG_MAX_GROUPS = 16;       // G <= 16 (aggregate.py MAX_GROUPS)
 constexpr int AGG_MAX_REGIONS = 64;      // R <= 64: a feature's regions are a 64-bit mask (aggregate.py MAX_REGIONS)
 constexpr int64_t AGG_MAX_TABLE = (int64_t)1 << 24;      // G P P K entries of either table (aggregate.py MAX_TABLE)
-constexpr int AGG_COORD_LIMIT = 1 << 30;
 constexpr int BAD_LABEL = 1, BAD_FLIP = 2, BAD_COORD = 4, BAD_EMPTY = 8;
 
 static_assert(2 * AGG_SMALL_AREA * AGG_MAX_REGIONS < 65536, "a 16-bit counter holds a small cell's histogram");
@@ -61,12 +59,6 @@ static_assert(128 * AGG_MAX_BODY * AGG_MAX_BODY < (1 << 24), "the multiply-shift
 struct AggRegion {
   long long lo;
   int H, W, s1, s2, diagonal, pad;
-};
-
-// first[g] .. first[g + 1]: the features of group g; chunk0[g]: the first chunk of group g, chunk0[G] the number of chunks
-struct AggGroups {
-  long long first[AGG_MAX_GROUPS + 1];
-  long long chunk0[AGG_MAX_GROUPS + 1];
 };
 
 struct AggGrid {
@@ -110,8 +102,7 @@ __device__ __forceinline__ bool agg_feature(const int32_t* __restrict__ feat, co
   ft->flip = flip ? flip[f] : 0;
   int w = 0;
   if (ft->flip > 1) w |= BAD_FLIP;
-  if (a0 <= -AGG_COORD_LIMIT || a0 >= AGG_COORD_LIMIT || a1 <= -AGG_COORD_LIMIT || a1 >= AGG_COORD_LIMIT || b0 <= -AGG_COORD_LIMIT ||
-      b0 >= AGG_COORD_LIMIT || b1 <= -AGG_COORD_LIMIT || b1 >= AGG_COORD_LIMIT)
+  if (coord_out(a0) || coord_out(a1) || coord_out(b0) || coord_out(b1))
     w |= BAD_COORD;
   else if (a1 <= a0 || b1 <= b0)
     w |= BAD_EMPTY;
@@ -145,29 +136,12 @@ __device__ __forceinline__ bool agg_feature(const int32_t* __restrict__ feat, co
 // rows [rlo, rhi) and columns [clo, chi) in chromosome bins -> local to the region and clipped; false: nothing stored there
 __device__ __forceinline__ bool agg_clip(const AggRegion& rg, long long rlo, long long rhi, long long clo, long long chi, int* i0,
                                          int* i1, int* j0, int* j1) {
-  long long x0 = rlo - rg.s1, x1 = rhi - rg.s1, y0 = clo - rg.s2, y1 = chi - rg.s2;
-  if (x0 < 0) x0 = 0;
-  if (x1 > rg.H) x1 = rg.H;
-  if (y0 < 0) y0 = 0;
-  if (y1 > rg.W) y1 = rg.W;
-  if (rg.diagonal && x1 > y1) x1 = y1;                 // a row at or below y1 holds no stored cell of the rectangle
-  if (x0 >= x1 || y0 >= y1) return false;
-  *i0 = (int)x0;
-  *i1 = (int)x1;
-  *j0 = (int)y0;
-  *j1 = (int)y1;
-  return true;
-}
-
-__device__ __forceinline__ int agg_group(const AggGroups& gr, int64_t f) {
-  int g = 0;
-  while (g < AGG_MAX_GROUPS - 1 && gr.first[g + 1] <= f) ++g;
-  return g;
+  return clip_rect(rg.H, rg.W, rg.diagonal, rlo - rg.s1, rhi - rg.s1, clo - rg.s2, chi - rg.s2, i0, i1, j0, j1);
 }
 
 // cells, votes: u64 [G][P P][K]
 __global__ __launch_bounds__(AGG_LANES) void aggregate_lane_kernel(const uint8_t* __restrict__ labels, const AggRegion* __restrict__ regs,
-                                                                   int R, int K, AggGrid gd, AggGroups gr,
+                                                                   int R, int K, AggGrid gd, GroupChunks gr,
                                                                    const int32_t* __restrict__ feat, const uint8_t* __restrict__ flip,
                                                                    int tiles, int64_t nitems, unsigned long long* __restrict__ cells,
                                                                    unsigned long long* __restrict__ votes, int* __restrict__ bad) {
@@ -182,7 +156,7 @@ __global__ __launch_bounds__(AGG_LANES) void aggregate_lane_kernel(const uint8_t
     const int64_t chunk = item / tiles;
     const int tile = (int)(item - chunk * tiles);
     int g = 0;
-    while (g < AGG_MAX_GROUPS - 1 && gr.chunk0[g + 1] <= chunk) ++g;                // (chunk < chunk0[G]; an empty group has no chunk)
+    while (g < MAX_GROUPS - 1 && gr.chunk0[g + 1] <= chunk) ++g;                    // (chunk < chunk0[G]; an empty group has no chunk)
     const int64_t a = gr.first[g] + (chunk - gr.chunk0[g]) * AGG_CHUNK;
     const int64_t b = a + AGG_CHUNK < gr.first[g + 1] ? a + AGG_CHUNK : gr.first[g + 1];
     const int cell = tile * AGG_LANES + (int)threadIdx.x;
@@ -213,7 +187,7 @@ __global__ __launch_bounds__(AGG_LANES) void aggregate_lane_kernel(const uint8_t
                 wrong |= BAD_LABEL;
                 continue;
               }
-              hist[(s >> 1) * AGG_LANES] += 1u << (16 * (s & 1));
+              packed_bump<AGG_LANES>(hist, s);
               any = true;
             }
           }
@@ -238,18 +212,11 @@ __global__ __launch_bounds__(AGG_LANES) void aggregate_lane_kernel(const uint8_t
         acc[(2 * q + 1) * AGG_LANES] += n1;
         hist[q * AGG_LANES] = 0;
       }
-      vote[(best >> 1) * AGG_LANES] += 1u << (16 * (best & 1));
+      packed_bump<AGG_LANES>(vote, best);
     }
     if (live) {
       const size_t at = ((size_t)g * S + cell) * K;
-      for (int q = 0; q < words; ++q) {
-        const unsigned n = vote[q * AGG_LANES];
-        if (n) {
-          if (n & 0xffffu) atomicAdd(votes + at + 2 * q, (unsigned long long)(n & 0xffffu));
-          if (n >> 16) atomicAdd(votes + at + 2 * q + 1, (unsigned long long)(n >> 16));  // (K odd: the last word's high half stays 0)
-          vote[q * AGG_LANES] = 0;
-        }
-      }
+      packed_flush<AGG_LANES>(vote, words, votes + at);
       for (int k = 0; k < K; ++k) {
         const unsigned n = acc[k * AGG_LANES];
         if (n) {
@@ -262,15 +229,9 @@ __global__ __launch_bounds__(AGG_LANES) void aggregate_lane_kernel(const uint8_t
   if (wrong) atomicOr(bad, wrong);
 }
 
-// the wave's LDS traffic in program order for every lane (the histogram is written by some lanes and read by others)
-__device__ __forceinline__ void agg_wave_order() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 __global__ __launch_bounds__(64 * AGG_WAVES) void aggregate_wave_kernel(const uint8_t* __restrict__ labels,
                                                                        const AggRegion* __restrict__ regs, int R, int K, AggGrid gd,
-                                                                       AggGroups gr, const int32_t* __restrict__ feat,
+                                                                       GroupChunks gr, const int32_t* __restrict__ feat,
                                                                        const uint8_t* __restrict__ flip, int64_t nitems,
                                                                        unsigned long long* __restrict__ cells,
                                                                        unsigned long long* __restrict__ votes, int* __restrict__ bad) {
@@ -278,7 +239,7 @@ __global__ __launch_bounds__(64 * AGG_WAVES) void aggregate_wave_kernel(const ui
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, P = gd.P;
   unsigned* const hist = hist_all[wave];
   hist[lane] = 0;
-  agg_wave_order();
+  wave_order();
   int wrong = 0, ignore = 0;
   for (int64_t item = blockIdx.x; item < nitems; item += gridDim.x) {
     const int64_t f = item / P;
@@ -286,7 +247,7 @@ __global__ __launch_bounds__(64 * AGG_WAVES) void aggregate_wave_kernel(const ui
     AggFeature ft;
     // (the lane kernel sees every feature and reports the malformed ones)
     if (!agg_feature(feat, flip, f, gd, regs, R, &ft, &ignore) || ft.small) continue;
-    const int g = agg_group(gr, f);
+    const int g = group_of_entry(gr, f);
     long long il, ih;
     agg_cell(ft.A, ft.flip ? P - 1 - u : u, gd, &il, &ih);
     for (int v = wave; v < P; v += AGG_WAVES) {
@@ -329,10 +290,10 @@ __global__ __launch_bounds__(64 * AGG_WAVES) void aggregate_wave_kernel(const ui
               }
             }
           }
-          agg_wave_order();                            // a clipped rectangle has fewer than 2^31 nodes: no bin has carried
+          wave_order();                            // a clipped rectangle has fewer than 2^31 nodes: no bin has carried
           total += hist[lane];
           hist[lane] = 0;
-          agg_wave_order();
+          wave_order();
         }
       }
       if (lane >= K) total = 0;                        // (no key is >= K: those bins stayed 0 anyway)
@@ -378,7 +339,7 @@ int phmrf_state_aggregate(const uint8_t* labels_dev, int64_t n_labels, int R, co
   PHMRF_TRY(check_states(K));
   PHMRF_CHECK(T <= AGG_MAX_BODY, PHMRF_ERR_UNSUPPORTED, "T must be <= 64");
   PHMRF_CHECK(F <= AGG_MAX_FLANK, PHMRF_ERR_UNSUPPORTED, "F must be <= 32");
-  PHMRF_CHECK(G <= AGG_MAX_GROUPS, PHMRF_ERR_UNSUPPORTED, "G must be <= 16");
+  PHMRF_CHECK(G <= MAX_GROUPS, PHMRF_ERR_UNSUPPORTED, "G must be <= 16");
   PHMRF_CHECK(R <= AGG_MAX_REGIONS, PHMRF_ERR_UNSUPPORTED, "R must be <= 64");
   const int P = T + 2 * F, S = P * P;
   const int64_t n_tab = (int64_t)G * S * K;
@@ -394,56 +355,45 @@ int phmrf_state_aggregate(const uint8_t* labels_dev, int64_t n_labels, int R, co
     PHMRF_TRY(check_nodes(n));
     PHMRF_CHECK(row[0] >= 0 && row[0] + n <= n_labels, PHMRF_ERR_INVALID, "a region's nodes must lie inside the labels");
     PHMRF_CHECK(row[3] >= 0 && row[4] >= 0, PHMRF_ERR_INVALID, "a region's start bins must be >= 0");
-    PHMRF_CHECK(row[3] < AGG_COORD_LIMIT && row[4] < AGG_COORD_LIMIT, PHMRF_ERR_UNSUPPORTED, "a region's start bins must be below 2^30");
+    PHMRF_CHECK(!coord_out(row[3]) && !coord_out(row[4]), PHMRF_ERR_UNSUPPORTED, "a region's start bins must be below 2^30");
     regs[(size_t)r] = AggRegion{(long long)row[0], (int)row[1], (int)row[2], (int)row[3], (int)row[4], (int)row[5], 0};
   }
-  PHMRF_CHECK(group_offsets_host[0] == 0, PHMRF_ERR_INVALID, "the group offsets must start at 0");
-  AggGroups gr;
-  for (int g = 0; g <= AGG_MAX_GROUPS; ++g) {
-    const int64_t at = group_offsets_host[g < G ? g : G];
-    PHMRF_CHECK(g == 0 || g > G || at >= group_offsets_host[g - 1], PHMRF_ERR_INVALID, "the group offsets must not decrease");
-    gr.first[g] = at;
-  }
-  const int64_t N = group_offsets_host[G];
-  PHMRF_CHECK(N < ((int64_t)1 << 31), PHMRF_ERR_UNSUPPORTED, "there must be fewer than 2^31 features");
+  GroupChunks gr;
+  int64_t N = 0;
+  PHMRF_TRY(group_first(group_offsets_host, G, "features", &gr, &N));
   PHMRF_CHECK(N == 0 || feat_dev, PHMRF_ERR_INVALID, "NULL features");
   if (N == 0) {
     for (int64_t t = 0; t < n_tab; ++t) cells_host[t] = votes_host[t] = 0;
     return PHMRF_OK;
   }
-  gr.chunk0[0] = 0;
-  for (int g = 0; g < AGG_MAX_GROUPS; ++g) gr.chunk0[g + 1] = gr.chunk0[g] + (gr.first[g + 1] - gr.first[g] + AGG_CHUNK - 1) / AGG_CHUNK;
+  group_chunks(&gr, AGG_CHUNK);
   const int tiles = (S + AGG_LANES - 1) / AGG_LANES;
   const int64_t lane_items = gr.chunk0[G] * tiles, wave_items = N * P;
   const AggGrid gd{T, F, P, (int)((((int64_t)1 << 24) + T - 1) / T)};
 
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  Buffers buf;                                         // cells | votes | the flag word: one allocation, one memset
-  unsigned long long* table;
+  Buffers buf;
+  FlaggedTable tab(st);                                // cells | votes
   AggRegion* regs_dev;
-  PHMRF_TRY(buf.get(&table, (size_t)(2 * n_tab + 1)));
+  PHMRF_TRY(tab.make(&buf, (size_t)(2 * n_tab)));
   PHMRF_TRY(buf.get(&regs_dev, (size_t)R));
-  int* const flag = reinterpret_cast<int*>(table + 2 * n_tab);
-  PHMRF_HIP(hipMemsetAsync(table, 0, (size_t)(2 * n_tab + 1) * sizeof(unsigned long long), st));
+  unsigned long long* const table = tab.words();
   PHMRF_HIP(hipMemcpyAsync(regs_dev, regs.data(), (size_t)R * sizeof(AggRegion), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(aggregate_lane_kernel, dim3(grid_of(lane_items, 1, AGG_GRID_CAP)), dim3(AGG_LANES), aggregate_lds_bytes(K), st,
-                     labels_dev, regs_dev, R, K, gd, gr, feat_dev, flip_dev_or_null, tiles, lane_items, table, table + n_tab, flag);
+                     labels_dev, regs_dev, R, K, gd, gr, feat_dev, flip_dev_or_null, tiles, lane_items, table, table + n_tab, tab.flag());
   PHMRF_HIP(hipGetLastError());
   hipLaunchKernelGGL(aggregate_wave_kernel, dim3(grid_of(wave_items, 1, AGG_WAVE_GRID_CAP)), dim3(64 * AGG_WAVES), 0, st, labels_dev,
-                     regs_dev, R, K, gd, gr, feat_dev, flip_dev_or_null, wave_items, table, table + n_tab, flag);
+                     regs_dev, R, K, gd, gr, feat_dev, flip_dev_or_null, wave_items, table, table + n_tab, tab.flag());
   PHMRF_HIP(hipGetLastError());
   int bad = 0;
-  PHMRF_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
-  PHMRF_HIP(hipStreamSynchronize(st));
+  PHMRF_TRY(tab.read_flag(&bad));
   PHMRF_CHECK(!(bad & BAD_FLIP), PHMRF_ERR_INVALID, "a flip is > 1");
   PHMRF_CHECK(!(bad & BAD_COORD), PHMRF_ERR_UNSUPPORTED, "a feature coordinate has |c| >= 2^30");
   PHMRF_CHECK(!(bad & BAD_EMPTY), PHMRF_ERR_INVALID, "a feature needs a1 > a0 and b1 > b0");
   PHMRF_CHECK(!(bad & BAD_LABEL), PHMRF_ERR_INVALID, "a label inside a feature's cell is >= K");
-  static_assert(sizeof(int64_t) == sizeof(unsigned long long), "the tables are copied as they are");
-  PHMRF_HIP(hipMemcpyAsync(cells_host, table, (size_t)n_tab * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  PHMRF_HIP(hipMemcpyAsync(votes_host, table + n_tab, (size_t)n_tab * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  PHMRF_HIP(hipStreamSynchronize(st));
-  return PHMRF_OK;
+  PHMRF_TRY(tab.copy(0, (size_t)n_tab, cells_host));
+  PHMRF_TRY(tab.copy((size_t)n_tab, (size_t)n_tab, votes_host));
+  return tab.wait();
 }
 
 }  // extern "C"

@@ -4,21 +4,19 @@
 //
 //   An ITEM is a tile of PILEUP_LANES consecutive pile cells (v fastest) times a CHUNK of at most PILEUP_CHUNK consecutive
 //   centres of ONE group; the items (the tile fastest, so that neighbouring workgroups walk the same centres) stride over a
-//   capped grid.  The groups' offsets and first chunks travel in the kernel's arguments (at most 17 of each).
+//   capped grid.  The groups' offsets and first chunks travel in the kernel's arguments (GroupChunks, interval_lists.h).
 //   lane <-> pile cell: for an untransposed centre the 64 lanes of a wave read contiguous pieces of at most two storage rows.
 //   The centre is the same for every lane (uniform loads), the label a one-byte gather; four centres' labels are loaded before
 //   the first of them is counted.  A centre whose whole window misses the region is passed over without a load.
-//   Every lane keeps a PRIVATE column of counters in LDS, laid out [k / 2][lane]: 16 bits a state, two states to a u32 word
-//   (a chunk has at most 256 centres: a counter never carries).  A lane only ever touches its own column, whose words fall on
-//   bank lane mod 32 of its half-wave: no LDS atomics, no bank conflicts and no barrier anywhere in the kernel.  At K = 64
-//   the columns take 32 KB.
-//   After the chunk a lane adds its non-zero counters to the device table with u64 atomics and zeroes them.
+//   Every lane keeps a private column of 16-bit counters in LDS (packed_bump / packed_flush, interval_lists.h; a chunk has at
+//   most 256 centres: a counter never carries): no LDS atomics, no bank conflicts and no barrier anywhere in the kernel.  At
+//   K = 64 the columns take 32 KB.  After the chunk a lane adds its non-zero counters to the device table and zeroes them.
 //   The label check is as in tracks.hip and enrich.hip: only a cell some window holds is looked at.  Flag bits: a label >= K
 //   on such a cell, an orient > 3, a coordinate with |c| >= 2^30 (such a centre is passed over).
 //   label_row (runs.h) does not fit: it describes a contiguous piece of ONE storage row per half-wave, the pile reads a
 //   single byte per lane and centre.
 
-#include "runs.h"
+#include "interval_lists.h"
 
 namespace phmrf {
 namespace {
@@ -27,24 +25,16 @@ constexpr int PILEUP_LANES = 256;        // pile cells of a tile = lanes of a wo
 constexpr int PILEUP_CHUNK = 256;        // centres of one group a workgroup piles before it adds to the table (pileup.py CHUNK)
 constexpr int PILEUP_GRID_CAP = 4096;    // workgroups (pileup.py GRID_CAP)
 constexpr int PILEUP_MAX_FLANK = 64;     // w <= 64 (pileup.py MAX_FLANK)
-constexpr int PILEUP_MAX_GROUPS = 16;    // G <= 16 (pileup.py MAX_GROUPS)
-constexpr int PILEUP_COORD_LIMIT = 1 << 30;
 constexpr int PILEUP_BATCH = 4;          // centres whose labels are in flight together
 constexpr int BAD_LABEL = 1, BAD_ORIENT = 2, BAD_COORD = 4;
 
 static_assert(PILEUP_CHUNK < 65536, "a 16-bit counter holds a chunk");
 
-// first[g] .. first[g + 1]: the centres of group g; chunk0[g]: the first chunk of group g, chunk0[G] the number of chunks
-struct PileGroups {
-  long long first[PILEUP_MAX_GROUPS + 1];
-  long long chunk0[PILEUP_MAX_GROUPS + 1];
-};
-
 inline size_t pileup_lds_bytes(int K) { return (size_t)((K + 1) / 2) * PILEUP_LANES * sizeof(unsigned); }
 
 // table: u64 [G][side side][K]
 __global__ __launch_bounds__(PILEUP_LANES) void pileup_kernel(const uint8_t* __restrict__ labels, int H, int W, int diagonal, int K,
-                                                              int w, PileGroups gr, const int32_t* __restrict__ ci,
+                                                              int w, GroupChunks gr, const int32_t* __restrict__ ci,
                                                               const int32_t* __restrict__ cj, const uint8_t* __restrict__ orient,
                                                               int tiles, int64_t nitems, unsigned long long* __restrict__ table,
                                                               int* __restrict__ bad) {
@@ -57,7 +47,7 @@ __global__ __launch_bounds__(PILEUP_LANES) void pileup_kernel(const uint8_t* __r
     const int64_t chunk = item / tiles;
     const int tile = (int)(item - chunk * tiles);
     int g = 0;
-    while (g < PILEUP_MAX_GROUPS - 1 && gr.chunk0[g + 1] <= chunk) ++g;             // (chunk < chunk0[G]; an empty group has no chunk)
+    while (g < MAX_GROUPS - 1 && gr.chunk0[g + 1] <= chunk) ++g;                    // (chunk < chunk0[G]; an empty group has no chunk)
     const int64_t a = gr.first[g] + (chunk - gr.chunk0[g]) * PILEUP_CHUNK;
     const int64_t b = a + PILEUP_CHUNK < gr.first[g + 1] ? a + PILEUP_CHUNK : gr.first[g + 1];
     const int cell = tile * PILEUP_LANES + (int)threadIdx.x;
@@ -72,7 +62,7 @@ __global__ __launch_bounds__(PILEUP_LANES) void pileup_kernel(const uint8_t* __r
         const int ai = ci[c + e], aj = cj[c + e];
         const int o = orient ? orient[c + e] : 0;
         if (o > 3) wrong |= BAD_ORIENT;
-        if (ai <= -PILEUP_COORD_LIMIT || ai >= PILEUP_COORD_LIMIT || aj <= -PILEUP_COORD_LIMIT || aj >= PILEUP_COORD_LIMIT) {
+        if (coord_out(ai) || coord_out(aj)) {
           wrong |= BAD_COORD;
           continue;
         }
@@ -94,20 +84,10 @@ __global__ __launch_bounds__(PILEUP_LANES) void pileup_kernel(const uint8_t* __r
           wrong |= BAD_LABEL;
           continue;
         }
-        mine[(s[e] >> 1) * PILEUP_LANES] += 1u << (16 * (s[e] & 1));
+        packed_bump<PILEUP_LANES>(mine, s[e]);
       }
     }
-    if (live) {
-      unsigned long long* const out = table + ((size_t)g * S + cell) * K;
-      for (int q = 0; q < words; ++q) {
-        const unsigned n = mine[q * PILEUP_LANES];
-        if (n) {
-          if (n & 0xffffu) atomicAdd(out + 2 * q, (unsigned long long)(n & 0xffffu));
-          if (n >> 16) atomicAdd(out + 2 * q + 1, (unsigned long long)(n >> 16));      // (K odd: the last word's high half stays 0)
-          mine[q * PILEUP_LANES] = 0;
-        }
-      }
-    }
+    if (live) packed_flush<PILEUP_LANES>(mine, words, table + ((size_t)g * S + cell) * K);
   }
   if (wrong) atomicOr(bad, wrong);
 }
@@ -130,17 +110,11 @@ int phmrf_state_pileup(const uint8_t* labels_dev, int H, int W, int diagonal, in
   PHMRF_CHECK(G >= 1, PHMRF_ERR_INVALID, "G must be >= 1");
   PHMRF_TRY(check_states(K));
   PHMRF_CHECK(w <= PILEUP_MAX_FLANK, PHMRF_ERR_UNSUPPORTED, "w must be <= 64");
-  PHMRF_CHECK(G <= PILEUP_MAX_GROUPS, PHMRF_ERR_UNSUPPORTED, "G must be <= 16");
+  PHMRF_CHECK(G <= MAX_GROUPS, PHMRF_ERR_UNSUPPORTED, "G must be <= 16");
   PHMRF_TRY(check_nodes(n, "n must be below 2^31 - 64"));
-  PHMRF_CHECK(group_offsets_host[0] == 0, PHMRF_ERR_INVALID, "the group offsets must start at 0");
-  PileGroups gr;
-  for (int g = 0; g <= PILEUP_MAX_GROUPS; ++g) {
-    const int64_t at = group_offsets_host[g < G ? g : G];
-    PHMRF_CHECK(g == 0 || g > G || at >= group_offsets_host[g - 1], PHMRF_ERR_INVALID, "the group offsets must not decrease");
-    gr.first[g] = at;
-  }
-  const int64_t n_centres = group_offsets_host[G];
-  PHMRF_CHECK(n_centres < ((int64_t)1 << 31), PHMRF_ERR_UNSUPPORTED, "there must be fewer than 2^31 centres");
+  GroupChunks gr;
+  int64_t n_centres = 0;
+  PHMRF_TRY(group_first(group_offsets_host, G, "centres", &gr, &n_centres));
   PHMRF_CHECK(n_centres == 0 || (ci_dev && cj_dev), PHMRF_ERR_INVALID, "NULL centre coordinates");
   const int side = 2 * w + 1, S = side * side;
   const size_t n_obs = (size_t)G * S * K;
@@ -148,31 +122,24 @@ int phmrf_state_pileup(const uint8_t* labels_dev, int H, int W, int diagonal, in
     for (size_t t = 0; t < n_obs; ++t) obs_host[t] = 0;
     return PHMRF_OK;
   }
-  gr.chunk0[0] = 0;
-  for (int g = 0; g < PILEUP_MAX_GROUPS; ++g)
-    gr.chunk0[g + 1] = gr.chunk0[g] + (gr.first[g + 1] - gr.first[g] + PILEUP_CHUNK - 1) / PILEUP_CHUNK;
+  group_chunks(&gr, PILEUP_CHUNK);
   const int tiles = (S + PILEUP_LANES - 1) / PILEUP_LANES;
   const int64_t nitems = gr.chunk0[G] * tiles;
 
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  Buffers buf;                                         // the table and, behind it, the flag word: one allocation, one memset
-  unsigned long long* table;
-  PHMRF_TRY(buf.get(&table, n_obs + 1));
-  int* const flag = reinterpret_cast<int*>(table + n_obs);
-  PHMRF_HIP(hipMemsetAsync(table, 0, (n_obs + 1) * sizeof(unsigned long long), st));
+  Buffers buf;
+  FlaggedTable tab(st);
+  PHMRF_TRY(tab.make(&buf, n_obs));
   hipLaunchKernelGGL(pileup_kernel, dim3(grid_of(nitems, 1, PILEUP_GRID_CAP)), dim3(PILEUP_LANES), pileup_lds_bytes(K), st, labels_dev,
-                     H, W, diagonal, K, w, gr, ci_dev, cj_dev, orient_dev_or_null, tiles, nitems, table, flag);
+                     H, W, diagonal, K, w, gr, ci_dev, cj_dev, orient_dev_or_null, tiles, nitems, tab.words(), tab.flag());
   PHMRF_HIP(hipGetLastError());
   int bad = 0;
-  PHMRF_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
-  PHMRF_HIP(hipStreamSynchronize(st));
+  PHMRF_TRY(tab.read_flag(&bad));
   PHMRF_CHECK(!(bad & BAD_ORIENT), PHMRF_ERR_INVALID, "an orient is > 3");
   PHMRF_CHECK(!(bad & BAD_COORD), PHMRF_ERR_UNSUPPORTED, "a centre coordinate has |c| >= 2^30");
   PHMRF_CHECK(!(bad & BAD_LABEL), PHMRF_ERR_INVALID, "a label inside a centre's window is >= K");
-  static_assert(sizeof(int64_t) == sizeof(unsigned long long), "the table is copied as it is");
-  PHMRF_HIP(hipMemcpyAsync(obs_host, table, n_obs * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  PHMRF_HIP(hipStreamSynchronize(st));
-  return PHMRF_OK;
+  PHMRF_TRY(tab.copy(0, n_obs, obs_host));
+  return tab.wait();
 }
 
 }  // extern "C"

@@ -20,7 +20,7 @@
 //   Only a node that some rectangle holds is looked at.  Flag bits: a label >= K on such a node, a confidence there that is no
 //   finite number in [0, 1].  Coordinates, slots and signs are checked on the host, where the rectangles are clipped.
 
-#include "runs.h"
+#include "interval_lists.h"
 
 namespace phmrf {
 namespace {
@@ -31,7 +31,6 @@ constexpr int RECT_VEC_MIN = 32;         // an item of at least this many column
 constexpr int RECT_WAVES = 4;            // waves of a workgroup, one item each (query.py WAVES)
 constexpr int RECT_GRID_CAP = 2048;      // workgroups (query.py GRID_CAP)
 constexpr int64_t RECT_BATCH = 1 << 20;  // items uploaded and launched together (query.py BATCH)
-constexpr int RECT_COORD_LIMIT = 1 << 30;
 constexpr int BAD_LABEL = 1, BAD_CONF = 2;
 
 static_assert(RECT_TILE_W == 4 * 64, "a row of an item is at most one word per lane");
@@ -42,12 +41,6 @@ static_assert((int64_t)RECT_TILE_H * RECT_TILE_W < ((int64_t)1 << 32), "a u32 bi
 struct RectItem {
   int32_t i0, i1, j0, j1, slot, minus;
 };
-
-// the wave's LDS traffic in program order for every lane (the histogram is written by some lanes and read by others)
-__device__ __forceinline__ void wave_order() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
 
 // counts: u64 [Q][K]; conf_sum: u64 [Q]
 __global__ __launch_bounds__(64 * RECT_WAVES) void rect_states_kernel(const uint8_t* __restrict__ labels, const float* __restrict__ conf,
@@ -158,23 +151,19 @@ int phmrf_rect_states(const uint8_t* labels_dev, const float* conf_dev_or_null, 
     PHMRF_CHECK(!minus_host_or_null || minus_host_or_null[t] <= 1, PHMRF_ERR_INVALID, "a minus byte is > 1");
   }
   for (int64_t t = 0; t < 4 * R; ++t)
-    PHMRF_CHECK(rect_host[t] > -RECT_COORD_LIMIT && rect_host[t] < RECT_COORD_LIMIT, PHMRF_ERR_UNSUPPORTED,
-                "a rectangle coordinate has |c| >= 2^30");
+    PHMRF_CHECK(!coord_out(rect_host[t]), PHMRF_ERR_UNSUPPORTED, "a rectangle coordinate has |c| >= 2^30");
 
-  const size_t n_counts = (size_t)Q * K, n_words = n_counts + (size_t)Q + 1;       // counts | confidence sums | the flag word
+  const size_t n_counts = (size_t)Q * K;                 // the table: counts | confidence sums
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   Buffers buf;
-  unsigned long long* table = nullptr;
+  FlaggedTable tab(st);
   RectItem* items_dev = nullptr;
   int64_t items_cap = 0;
   std::vector<RectItem> items;
   // uploads the items gathered so far and counts them; the first call makes the device tables
   auto flush = [&]() -> int {
     if (items.empty()) return PHMRF_OK;
-    if (!table) {
-      PHMRF_TRY(buf.get(&table, n_words));
-      PHMRF_HIP(hipMemsetAsync(table, 0, n_words * sizeof(unsigned long long), st));
-    }
+    if (!tab.made()) PHMRF_TRY(tab.make(&buf, n_counts + (size_t)Q));
     const int64_t m = (int64_t)items.size();
     if (m > items_cap) {                                 // (only a call's last batch is smaller than its first)
       PHMRF_TRY(buf.release(&items_dev));
@@ -183,21 +172,16 @@ int phmrf_rect_states(const uint8_t* labels_dev, const float* conf_dev_or_null, 
     }
     PHMRF_HIP(hipMemcpyAsync(items_dev, items.data(), (size_t)m * sizeof(RectItem), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(rect_states_kernel, dim3(grid_of(m, RECT_WAVES, RECT_GRID_CAP)), dim3(64 * RECT_WAVES), 0, st, labels_dev,
-                       conf_dev_or_null, W, diagonal, K, items_dev, m, table, table + n_counts,
-                       reinterpret_cast<int*>(table + n_counts + Q));
+                       conf_dev_or_null, W, diagonal, K, items_dev, m, tab.words(), tab.words() + n_counts, tab.flag());
     PHMRF_HIP(hipGetLastError());
     PHMRF_HIP(hipStreamSynchronize(st));                 // the host vector and the device table are taken again
     items.clear();
     return PHMRF_OK;
   };
   for (int64_t t = 0; t < R; ++t) {
-    int i0 = rect_host[4 * t], i1 = rect_host[4 * t + 1], j0 = rect_host[4 * t + 2], j1 = rect_host[4 * t + 3];
-    if (i0 < 0) i0 = 0;
-    if (i1 > H) i1 = H;
-    if (j0 < 0) j0 = 0;
-    if (j1 > W) j1 = W;
-    if (diagonal && i1 > j1) i1 = j1;                    // a row at or below j1 holds no stored cell of the rectangle
-    if (i0 >= i1 || j0 >= j1) continue;
+    int i0, i1, j0, j1;
+    if (!clip_rect(H, W, diagonal, rect_host[4 * t], rect_host[4 * t + 1], rect_host[4 * t + 2], rect_host[4 * t + 3], &i0, &i1, &j0, &j1))
+      continue;
     const int32_t slot = slot_host_or_null ? slot_host_or_null[t] : (int32_t)t;
     const int32_t minus = minus_host_or_null ? minus_host_or_null[t] : 0;
     for (int a = i0; a < i1; a += RECT_TILE_H) {
@@ -210,23 +194,19 @@ int phmrf_rect_states(const uint8_t* labels_dev, const float* conf_dev_or_null, 
     }
   }
   PHMRF_TRY(flush());
-  if (!table) {                                          // no rectangle holds a node
+  if (!tab.made()) {                                     // no rectangle holds a node
     for (size_t x = 0; x < n_counts; ++x) counts_host[x] = 0;
     if (conf_host_or_null)
       for (int64_t q = 0; q < Q; ++q) conf_host_or_null[q] = 0;
     return PHMRF_OK;
   }
   int bad = 0;
-  PHMRF_HIP(hipMemcpyAsync(&bad, table + n_counts + Q, sizeof(int), hipMemcpyDeviceToHost, st));
-  PHMRF_HIP(hipStreamSynchronize(st));
+  PHMRF_TRY(tab.read_flag(&bad));
   PHMRF_CHECK(!(bad & BAD_LABEL), PHMRF_ERR_INVALID, "a label inside a rectangle is >= K");
   PHMRF_CHECK(!(bad & BAD_CONF), PHMRF_ERR_INVALID, "a confidence inside a rectangle is not a finite number in [0, 1]");
-  static_assert(sizeof(int64_t) == sizeof(unsigned long long), "the tables are copied as they are");
-  PHMRF_HIP(hipMemcpyAsync(counts_host, table, n_counts * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  if (conf_host_or_null)
-    PHMRF_HIP(hipMemcpyAsync(conf_host_or_null, table + n_counts, (size_t)Q * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  PHMRF_HIP(hipStreamSynchronize(st));
-  return PHMRF_OK;
+  PHMRF_TRY(tab.copy(0, n_counts, counts_host));
+  if (conf_host_or_null) PHMRF_TRY(tab.copy(n_counts, (size_t)Q, conf_host_or_null));
+  return tab.wait();
 }
 
 }  // extern "C"

@@ -1,9 +1,11 @@
 // What the post-processing's kernel files share (smooth.hip, compare.hip, consensus.hip, profile.hip, domains.hip, tracks.hip,
-// enrich.hip, enrich_null.hip, pileup.hip, query.hip): the capped grid, the wave helpers of their integer accumulations -- one
-// atomic per RUN of equal destination among consecutive lanes, because state maps are piecewise constant --, the split of a
-// label row into aligned words (tracks, enrich, enrich_null, query) and the tiles of a distance window (tracks; enrich and
-// enrich_null through enrich_tiles.h), the full-matrix area of a grid component, and on the host the owner of a call's device
-// buffers and the checks of a region's and a window's arguments (preprocess.hip and render.hip take those too).
+// enrich.hip, enrich_null.hip, pileup.hip, query.hip, aggregate.hip): the capped grid, the wave helpers of their integer
+// accumulations -- one atomic per RUN of equal destination among consecutive lanes, because state maps are piecewise constant
+// --, the split of a label row into aligned words (tracks, enrich, enrich_null, query, aggregate), the order of a wave's LDS
+// traffic (query, aggregate) and the tiles of a distance window (tracks; enrich and enrich_null through enrich_tiles.h), the
+// full-matrix area of a grid component, and on the host the owner of a call's device buffers and the
+// checks of a region's and a window's arguments (preprocess.hip and render.hip take those too).  What only the interval-list
+// kernels share (pileup, query, aggregate) is in interval_lists.h.
 #pragma once
 
 #include "common.h"
@@ -93,6 +95,12 @@ __device__ __forceinline__ LabelRow label_row(const uint8_t* __restrict__ labels
 __device__ __forceinline__ void load_row(const LabelRow& r, int q, uint32_t* word, int* single) {
   if (q < r.nvec) *word = *reinterpret_cast<const uint32_t*>(r.p + r.head + 4 * q);
   if (q < r.nbytes) *single = r.p[r.byte_at(q)];
+}
+
+// a wave's LDS traffic in program order for every lane (its histogram is written by some lanes and read by others)
+__device__ __forceinline__ void wave_order() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
 }
 
 // band of a distance d >= 0: 0 for d == 0, else t with 2^(t-1) <= d < 2^t (PHMRF_DIFF_BANDS of them below 2^31)

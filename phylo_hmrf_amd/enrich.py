@@ -29,7 +29,8 @@ import os
 
 import numpy as np
 
-from .maps import MAX_STATES, check_len_vec, check_state_vec, chrom_of, device, load_map, stem
+from .intervals import held_chrom, interval_lines, name_group
+from .maps import MAX_STATES, check_K, check_len_vec, check_resolution, check_state_vec, device, load_map, stem
 from .tracks import check_windows, covered_bins, parse_windows
 
 GRID_CAP = 1024                  # csrc/enrich.hip ENRICH_GRID_CAP: workgroups (of 256 lanes) of its kernels
@@ -104,9 +105,6 @@ def fold_pairs(table, C):
     return out
 
 
-_chrom_of = chrom_of
-
-
 def read_annotation(path, len_vec, resolution, segments=False):
     """A BED-like text file `chrom start stop name` (tabs or spaces; lines that start with # and blank lines are skipped) ->
     dict:
@@ -118,46 +116,30 @@ def read_annotation(path, len_vec, resolution, segments=False):
     chrom is chr<N> or <N>, N the integer in len_vec's column 9.  A bin g takes the FIRST line in file order whose
     [start, stop) holds its midpoint g res + res // 2.  The names are numbered over the whole file, whatever chromosomes
     len_vec holds.  ValueError for a malformed line, start >= stop, a negative coordinate and more than 7 names.  Host only."""
-    res = int(resolution)
-    if res < 1:
-        raise ValueError("resolution must be >= 1")
+    res = check_resolution(resolution)
     L = np.asarray(len_vec)
     bin_class = {int(c): np.zeros(covered_bins(L, c).shape[0], dtype=np.uint8) for c in np.unique(L[:, 9])}
     bin_seg = {c: np.full(v.shape[0], -1, dtype=np.int32) for c, v in bin_class.items()} if segments else None
     taken = {c: np.zeros(v.shape[0], dtype=bool) for c, v in bin_class.items()}
-    names, skipped, kept = ["none"], 0, 0
-    with open(path) as fh:
-        for number, line in enumerate(fh, 1):
-            f = line.split()
-            if not f or f[0].startswith("#"):
-                continue
-            if len(f) < 4 or not f[1].lstrip("-").isdigit() or not f[2].lstrip("-").isdigit():
-                raise ValueError("%s line %d: expected `chrom start stop name`, got %r" % (path, number, line.rstrip("\n")))
-            start, stop = int(f[1]), int(f[2])
-            if start < 0 or stop < 0:
-                raise ValueError("%s line %d: negative coordinate" % (path, number))
-            if start >= stop:
-                raise ValueError("%s line %d: start %d >= stop %d" % (path, number, start, stop))
-            if f[3] not in names[1:]:
-                if len(names) == MAX_CLASSES:
-                    raise ValueError("%s line %d: more than %d names (%s, then %r): at most %d classes beside `none` are "
-                                     "supported" % (path, number, MAX_CLASSES - 1, ", ".join(names[1:]), f[3], MAX_CLASSES - 1))
-                names.append(f[3])
-            c = _chrom_of(f[0])
-            if c not in bin_class:
-                skipped += 1
-                continue
-            B, half = bin_class[c].shape[0], res // 2
-            g0 = min(B, max(0, -(-(start - half) // res)))          # the first g with g res + half >= start
-            g1 = min(B, max(0, -(-(stop - half) // res)))           # the first g with g res + half >= stop
-            if g1 > g0:
-                free = ~taken[c][g0:g1]
-                bin_class[c][g0:g1][free] = names.index(f[3], 1)
-                if segments:
-                    bin_seg[c][g0:g1][free] = kept
-                taken[c][g0:g1] = True
-            kept += 1
-    return dict(bin_class=bin_class, bin_seg=bin_seg, names=names, skipped_lines=skipped)
+    names, skipped, kept = [], 0, 0                           # (the file's names: class 0, `none`, is not among them)
+    why = ": at most %d classes beside `none` are supported" % (MAX_CLASSES - 1)
+    for number, _, chroms, ((start, stop),), rest in interval_lines(path, 1, "chrom start stop name", False, fields=4):
+        cls = 1 + name_group(path, number, names, rest[0], MAX_CLASSES - 1, why)
+        c = held_chrom(chroms, bin_class)
+        if c is None:
+            skipped += 1
+            continue
+        B, half = bin_class[c].shape[0], res // 2
+        g0 = min(B, max(0, -(-(start - half) // res)))          # the first g with g res + half >= start
+        g1 = min(B, max(0, -(-(stop - half) // res)))           # the first g with g res + half >= stop
+        if g1 > g0:
+            free = ~taken[c][g0:g1]
+            bin_class[c][g0:g1][free] = cls
+            if segments:
+                bin_seg[c][g0:g1][free] = kept
+            taken[c][g0:g1] = True
+        kept += 1
+    return dict(bin_class=bin_class, bin_seg=bin_seg, names=["none"] + names, skipped_lines=skipped)
 
 
 def _slice(table, chrom, start, count, fill, dtype):
@@ -201,9 +183,7 @@ def pair_enrichment(state_vec, len_vec, bin_class, bin_seg=None, window=(0, -1),
     s = check_state_vec(state_vec)
     L = check_len_vec(len_vec, s.shape[0])
     d_min, d_max = (int(x) for x in check_windows([tuple(window)])[0])
-    K = (int(s.max()) + 1 if s.size else 1) if K is None else int(K)
-    if K < 1 or K > MAX_STATES:
-        raise ValueError("K must be in 1 .. %d" % MAX_STATES)
+    K = check_K(s, K)
     classes = _int_table(bin_class, "bin_class", 0, 255)
     segs = _int_table(bin_seg, "bin_seg", -1, 2 ** 31 - 1)
     C = max([1] + [int(v.max()) + 1 for v in classes.values() if v.size]) if C is None else int(C)

@@ -1,7 +1,7 @@
-"""What the post-processing modules share (smooth, compare, domains, tracks, render, enrich, pileup, query): the checks of a state
-map and its regions, the walk over the regions, the lines of an annotation file, the GPU handle and the protocol of the calls
-that list rows.  Host only apart from
-`device()`.
+"""What the post-processing modules share (smooth, compare, domains, tracks, render, enrich, pileup, query, aggregate): the
+checks of a state map, its regions and its number of states, the walk over the regions, the lines of an annotation file, the
+GPU handle and the protocol of the calls that list rows; what only the modes that read a list of intervals share is in
+intervals.py.  Host only apart from `device()`.
 
 len_vec rows: [n, start, stop, H, W, start_bin1, start_bin2, region_id, type (1 = diagonal), chrom].
 """
@@ -37,6 +37,14 @@ def check_state_vec(state_vec):
     if s.size and (s.min() < 0 or s.max() >= MAX_STATES):
         raise ValueError("state_vec must hold states in [0, %d) (got %d .. %d)" % (MAX_STATES, s.min(), s.max()))
     return s
+
+
+def check_K(s, K):
+    """-> K: the largest state of the checked states s + 1 by default (1 without any), in 1 .. MAX_STATES"""
+    K = (int(s.max()) + 1 if s.size else 1) if K is None else int(K)
+    if K < 1 or K > MAX_STATES:
+        raise ValueError("K must be in 1 .. %d" % MAX_STATES)
+    return K
 
 
 def check_len_vec(len_vec, n_states):

@@ -17,20 +17,19 @@ len_vec rows: [n, start, stop, H, W, start_bin1, start_bin2, region_id, type (1 
 """
 import ctypes
 import os
-import re
 
 import numpy as np
 
-from .maps import MAX_STATES, check_len_vec, check_state_vec, chrom_of, device, load_map, regions, stem
-from .maps import annotation_lines as _lines, check_resolution as _resolution, is_number as _number
-from .render import default_palette, load_palette, write_png
+from .intervals import (MAX_GROUPS, MAX_NAMES, check_G, check_shift, held_chrom, held_chroms, interval_lines, log2_ratio, name_group,
+                        pile_summary, shift_along_diagonal, summary_fields, write_group_images)
+from .maps import check_K, check_len_vec, check_state_vec, device, load_map, regions, stem
+from .maps import check_resolution as _resolution
+from .render import default_palette, load_palette
 
 LANES = 256                      # csrc/pileup.hip PILEUP_LANES: pile cells of a tile = lanes of a workgroup
 CHUNK = 256                      # csrc/pileup.hip PILEUP_CHUNK: centres of one group a workgroup piles at a time
 GRID_CAP = 4096                  # csrc/pileup.hip PILEUP_GRID_CAP: workgroups
 MAX_FLANK = 64                   # csrc/pileup.hip PILEUP_MAX_FLANK: w <= 64 bins on either side of a centre
-MAX_GROUPS = 16                  # csrc/pileup.hip PILEUP_MAX_GROUPS: 8 names and their 8 controls
-MAX_NAMES = 8
 FLIP, TRANSPOSE = 1, 2           # the bits of an orient
 PIXELS = 8                       # side of a pile cell in pileup_*.png
 
@@ -93,12 +92,8 @@ def state_pileup(state_vec, len_vec, centres, flank, K=None, G=None):
     L = check_len_vec(len_vec, s.shape[0])
     w = _check_flank(flank)
     c = _check_centres(centres)
-    K = (int(s.max()) + 1 if s.size else 1) if K is None else int(K)
-    if K < 1 or K > MAX_STATES:
-        raise ValueError("K must be in 1 .. %d" % MAX_STATES)
-    G = (int(c[:, 3].max()) + 1 if c.shape[0] else 1) if G is None else int(G)
-    if G < 1 or G > MAX_GROUPS:
-        raise ValueError("G must be in 1 .. %d" % MAX_GROUPS)
+    K = check_K(s, K)
+    G = check_G(c[:, 3], G)
     if c.shape[0] and c[:, 3].max() >= G:
         raise ValueError("a centre's group must be below G = %d" % G)
     lib, dev, stream = device()
@@ -122,24 +117,6 @@ def state_pileup(state_vec, len_vec, centres, flank, K=None, G=None):
 
 
 # ---- the anchor files -------------------------------------------------------------------------------------------------------
-def _interval(path, number, start, stop):
-    """-> the midpoint of [start, stop) in bp"""
-    start, stop = int(start), int(stop)
-    if start < 0 or stop < 0:
-        raise ValueError("%s line %d: negative coordinate" % (path, number))
-    if start >= stop:
-        raise ValueError("%s line %d: start %d >= stop %d" % (path, number, start, stop))
-    return (start + stop) // 2
-
-
-def _group(path, number, names, name):
-    if name not in names:
-        if len(names) == MAX_NAMES:
-            raise ValueError("%s line %d: more than %d names (%s, then %r)" % (path, number, MAX_NAMES, ", ".join(names), name))
-        names.append(name)
-    return names.index(name)
-
-
 def _anchors(rows, names, skipped):
     return dict(centres=np.array(rows, dtype=np.int64).reshape(-1, 5), names=names, skipped_lines=skipped)
 
@@ -154,19 +131,16 @@ def read_anchors(path, len_vec, resolution):
     chrom is chr<N> or <N>, N the integer in len_vec's column 9.  Strand - gives orient 1 (flip: the pile is read against the
     genome's direction); +, . and no strand give 0.  The names are numbered over the whole file.  ValueError for a malformed
     line, start >= stop, a negative coordinate, any other strand and a ninth name.  Host only."""
-    res = _resolution(resolution)
-    held = set(int(c) for c in np.unique(np.asarray(len_vec)[:, 9]))
+    res, held = _resolution(resolution), held_chroms(len_vec)
     rows, names, skipped = [], [], 0
-    for number, line, f in _lines(path):
-        if len(f) < 3 or not _number(f[1]) or not _number(f[2]):
-            raise ValueError("%s line %d: expected `chrom start stop [name [score [strand]]]`, got %r" % (path, number, line))
-        mid = _interval(path, number, f[1], f[2])
-        strand = f[5] if len(f) > 5 else "."
+    for number, _, chroms, ((start, stop),), rest in interval_lines(path, 1, "chrom start stop [name [score [strand]]]", False):
+        mid = (start + stop) // 2
+        strand = rest[2] if len(rest) > 2 else "."
         if strand not in ("+", "-", "."):
             raise ValueError("%s line %d: strand %r is not +, - or ." % (path, number, strand))
-        g = _group(path, number, names, f[3] if len(f) > 3 else "anchor")
-        c = chrom_of(f[0])
-        if c not in held:
+        g = name_group(path, number, names, rest[0] if rest else "anchor")
+        c = held_chrom(chroms, held)
+        if c is None:
             skipped += 1
             continue
         rows.append([c, mid // res, mid // res, g, FLIP if strand == "-" else 0])
@@ -177,16 +151,13 @@ def read_anchor_pairs(path, len_vec, resolution):
     """A BEDPE file `chrom1 start1 stop1 chrom2 start2 stop2 [name]` -> read_anchors' dict with the centres chrom, a, b, group,
     0: a <= b the bins of the two intervals' midpoints.  A line whose two ends are not on one chromosome of len_vec is
     skipped and counted; a line without a name is named `pair`.  Host only."""
-    res = _resolution(resolution)
-    held = set(int(c) for c in np.unique(np.asarray(len_vec)[:, 9]))
+    res, held = _resolution(resolution), held_chroms(len_vec)
     rows, names, skipped = [], [], 0
-    for number, line, f in _lines(path):
-        if len(f) < 6 or not all(_number(f[t]) for t in (1, 2, 4, 5)):
-            raise ValueError("%s line %d: expected `chrom1 start1 stop1 chrom2 start2 stop2 [name]`, got %r" % (path, number, line))
-        a, b = _interval(path, number, f[1], f[2]) // res, _interval(path, number, f[4], f[5]) // res
-        g = _group(path, number, names, f[6] if len(f) > 6 else "pair")
-        c = chrom_of(f[0])
-        if c not in held or chrom_of(f[3]) != c:
+    for number, _, chroms, spans, rest in interval_lines(path, 2, "chrom1 start1 stop1 chrom2 start2 stop2 [name]", False):
+        a, b = ((start + stop) // 2 // res for start, stop in spans)
+        g = name_group(path, number, names, rest[0] if rest else "pair")
+        c = held_chrom(chroms, held)
+        if c is None:
             skipped += 1
             continue
         rows.append([c, min(a, b), max(a, b), g, 0])
@@ -198,51 +169,15 @@ def with_controls(centres, shift_bins, G):
     (a + shift, b + shift) of group G + g with the same orient: shifted ALONG the diagonal, so at the centre's own genomic
     distance.  A control with a negative bin is dropped.  Host only."""
     c = _check_centres(centres)
-    shift, G = int(shift_bins), int(G)
-    if shift < 1:
-        raise ValueError("shift_bins must be >= 1")
+    ctl, keep = shift_along_diagonal(c, ((1,), (2,)), shift_bins)
+    G = int(G)
     if G < 1 or (c.shape[0] and c[:, 3].max() >= G):
         raise ValueError("G must be >= 1 and above every centre's group")
-    both = np.stack([c, c], axis=1)                           # per centre: the control before it, the control after it
-    both[:, 0, 1:3] -= shift
-    both[:, 1, 1:3] += shift
-    both[:, :, 3] += G
-    ctl = both.reshape(-1, 5)
-    return np.concatenate([c, ctl[(ctl[:, 1] >= 0) & (ctl[:, 2] >= 0)]])
+    ctl[:, 3] += G
+    return np.concatenate([c, ctl[keep]])
 
 
 # ---- reading a pile ---------------------------------------------------------------------------------------------------------
-def pile_summary(obs):
-    """obs [..., K] -> dict over the pile cells: total int64, dominant int64 (the state with the largest count, the lowest on
-    ties, -1 for an empty cell), share float64 (the dominant state's; 0 for an empty cell), entropy float64 in bits (0 for
-    an empty cell).  Host only."""
-    o = np.asarray(obs).astype(np.int64)
-    total = o.sum(axis=-1)
-    full = total > 0
-    dominant = np.where(full, np.argmax(o, axis=-1), -1)
-    p = np.divide(o, total[..., None], out=np.zeros(o.shape), where=full[..., None])
-    logp = np.zeros(o.shape)
-    np.log2(p, out=logp, where=p > 0)
-    return dict(total=total, dominant=dominant, share=p.max(axis=-1) if o.shape[-1] else np.zeros(total.shape),
-                entropy=np.abs((p * logp).sum(axis=-1)))
-
-
-def log2_ratio(obs, ctl):
-    """-> log2(share_obs / share_ctl + 1e-16) per pile cell and state, share = count / the cell's total; NaN where either
-    total is 0 or the control's share is 0.  Host only."""
-    o, c = np.asarray(obs, dtype=np.float64), np.asarray(ctl, dtype=np.float64)
-    if o.shape != c.shape:
-        raise ValueError("log2_ratio takes two piles of one shape (got %s and %s)" % (o.shape, c.shape))
-    to, tc = o.sum(axis=-1, keepdims=True), c.sum(axis=-1, keepdims=True)
-    ok = (to > 0) & (tc > 0) & (c > 0)
-    share_o = np.divide(o, to, out=np.zeros(o.shape), where=ok)
-    share_c = np.divide(c, tc, out=np.ones(o.shape), where=ok)
-    ratio = np.divide(share_o, share_c, out=np.zeros(o.shape), where=ok)
-    out = np.full(o.shape, np.nan)
-    np.log2(ratio + 1e-16, out=out, where=ok)
-    return out
-
-
 def pileup_lines(obs, names, flank, resolution, ctl=None):
     """-> the lines of pileup_*.txt, header first: per group and pile cell the name, u and v in bp, the total, the dominant
     state + 1 (0 for an empty cell), its share, the entropy in bits, with a control the control's total and the log2 ratio of
@@ -250,21 +185,13 @@ def pileup_lines(obs, names, flank, resolution, ctl=None):
     o = np.asarray(obs)
     G, side, _, K = o.shape
     w, res = int(flank), int(resolution)
-    sm = pile_summary(o)
-    head = ["#name", "u_bp", "v_bp", "total", "dominant_state", "share", "entropy_bits"]
-    if ctl is not None:
-        head += ["control_total", "log2_ratio"]
-        ctl_total, l2 = np.asarray(ctl).sum(axis=-1), log2_ratio(o, ctl)
-    lines = ["\t".join(head + ["state_%d" % (k + 1) for k in range(K)]) + "\n"]
+    (core_head, tail_head), fields = summary_fields(o, ctl)
+    lines = ["\t".join(["#name", "u_bp", "v_bp", "total"] + core_head + tail_head) + "\n"]
     for g in range(G):
         for a in range(side):
             for b in range(side):
-                dom = int(sm["dominant"][g, a, b])
-                f = [names[g], "%d" % ((a - w) * res), "%d" % ((b - w) * res), "%d" % sm["total"][g, a, b], "%d" % (dom + 1),
-                     "%.6f" % sm["share"][g, a, b], "%.6f" % sm["entropy"][g, a, b]]
-                if ctl is not None:
-                    f += ["%d" % ctl_total[g, a, b], "%.4f" % (l2[g, a, b, dom] if dom >= 0 else np.nan)]
-                lines.append("\t".join(f + ["%d" % x for x in o[g, a, b]]) + "\n")
+                core, tail = fields((g, a, b))
+                lines.append("\t".join([names[g], "%d" % ((a - w) * res), "%d" % ((b - w) * res)] + core + tail) + "\n")
     return lines
 
 
@@ -278,12 +205,10 @@ def pile_image(obs_g, palette):
 
 def check_bins(resolution, flank_bp, shift_bp):
     """-> (w, shift) in bins: w = flank_bp // resolution in 0 .. 64; a shift is a whole number of bins (0: no controls)"""
-    res, flank_bp, shift_bp = _resolution(resolution), int(flank_bp), int(shift_bp)
+    res, flank_bp = _resolution(resolution), int(flank_bp)
     if flank_bp < 0 or flank_bp // res > MAX_FLANK:
         raise ValueError("the flank must be 0 .. %d bins of %d bp, not %d bp" % (MAX_FLANK, res, flank_bp))
-    if shift_bp < 0 or shift_bp % res:
-        raise ValueError("the shift must be a whole number of bins of %d bp (0: no controls), not %d bp" % (res, shift_bp))
-    return flank_bp // res, shift_bp // res
+    return flank_bp // res, check_shift(res, shift_bp)
 
 
 def pileup_files(path, output_path, resolution, field="state_vec", bed="", bedpe="", flank_bp=1000000, shift_bp=0, palette_path=""):
@@ -318,11 +243,5 @@ def pileup_files(path, output_path, resolution, field="state_vec", bed="", bedpe
              palette=palette, **extra)
     with open(os.path.join(output_path, "pileup_%s.txt" % name), "wb") as fh:
         fh.write("".join(pileup_lines(obs, names, w, res, ctl)).encode())
-    used = set()
-    for g, group in enumerate(names):
-        safe = re.sub(r"[^A-Za-z0-9._-]", "_", group)
-        if safe in used:
-            safe = "%s_g%d" % (safe, g)
-        used.add(safe)
-        write_png(os.path.join(output_path, "pileup_%s_%s.png" % (name, safe)), pile_image(obs[g], palette))
+    write_group_images(output_path, "pileup_%s" % name, names, [pile_image(obs[g], palette) for g in range(G)])
     return out

@@ -29,9 +29,9 @@ import os
 
 import numpy as np
 
-from .maps import (CONF_ONE, MAX_STATES, annotation_lines, check_len_vec, check_resolution, check_state_vec, chrom_of, conf_array,
-                   device, is_number, load_map, regions, stem)
-from .pileup import check_bins, log2_ratio, pile_summary
+from .intervals import (check_shift, held_chrom, held_chroms, interval_lines, log2_ratio, overlap_bins, pile_summary, shift_along_diagonal,
+                        summary_fields)
+from .maps import CONF_ONE, check_K, check_len_vec, check_resolution, check_state_vec, conf_array, device, load_map, regions, stem
 
 TILE_H = 16                      # csrc/query.hip RECT_TILE_H: storage rows of an item, the piece of a rectangle one wave takes
 TILE_W = 256                     # csrc/query.hip RECT_TILE_W: storage columns of an item
@@ -39,7 +39,7 @@ VEC_MIN = 32                     # csrc/query.hip RECT_VEC_MIN: an item at least
 WAVES = 4                        # csrc/query.hip RECT_WAVES: waves of a workgroup
 GRID_CAP = 2048                  # csrc/query.hip RECT_GRID_CAP: workgroups
 BATCH = 1 << 20                  # csrc/query.hip RECT_BATCH: items uploaded and launched together
-COORD_LIMIT = 1 << 30            # csrc/query.hip RECT_COORD_LIMIT: |c| of a rectangle's coordinate stays below it
+COORD_LIMIT = 1 << 30            # csrc/interval_lists.h COORD_LIMIT: |c| of a rectangle's coordinate stays below it
 
 
 def _check_queries(queries):
@@ -69,14 +69,7 @@ def with_controls(queries, shift_bins):
     ALONG the diagonal -- both intervals move together, so every bin pair keeps its genomic distance --, the one before its
     query first; owner[c] is the index of control c's query.  A control with a negative bin is dropped.  Host only."""
     q = _check_queries(queries)
-    shift = int(shift_bins)
-    if shift < 1:
-        raise ValueError("shift_bins must be >= 1")
-    both = np.stack([q, q], axis=1)
-    both[:, 0, 1:] -= shift
-    both[:, 1, 1:] += shift
-    ctl = both.reshape(-1, 5)
-    keep = (ctl[:, 1] >= 0) & (ctl[:, 3] >= 0)
+    ctl, keep = shift_along_diagonal(q, ((1, 2), (3, 4)), shift_bins)
     return ctl[keep], np.repeat(np.arange(q.shape[0], dtype=np.int64), 2)[keep]
 
 
@@ -140,9 +133,7 @@ def state_query(state_vec, len_vec, queries, K=None, conf=None):
     s = check_state_vec(state_vec)
     L = check_len_vec(len_vec, s.shape[0])
     q = _check_queries(queries)
-    K = (int(s.max()) + 1 if s.size else 1) if K is None else int(K)
-    if K < 1 or K > MAX_STATES:
-        raise ValueError("K must be in 1 .. %d" % MAX_STATES)
+    K = check_K(s, K)
     Q = q.shape[0]
     c = None if conf is None else conf_array(conf, s.shape[0], "conf")
     counts = np.zeros((Q, K), dtype=np.int64)
@@ -166,17 +157,6 @@ def state_query(state_vec, len_vec, queries, K=None, conf=None):
 
 
 # ---- the interval files -----------------------------------------------------------------------------------------------------
-def _bins(path, number, start, stop, res):
-    """-> (start, stop, a0, a1): the bins [a0, a1) that [start, stop) bp overlaps, at least one"""
-    start, stop = int(start), int(stop)
-    if start < 0 or stop < 0:
-        raise ValueError("%s line %d: negative coordinate" % (path, number))
-    if stop < start:
-        raise ValueError("%s line %d: stop %d < start %d" % (path, number, stop, start))
-    a0 = start // res
-    return start, stop, a0, max(a0 + 1, -(-stop // res))
-
-
 def _read(rows, names, lines, skipped):
     return dict(queries=np.array(rows, dtype=np.int64).reshape(-1, 5), names=names, lines=lines, skipped_lines=skipped)
 
@@ -190,20 +170,16 @@ def read_intervals(path, len_vec, resolution):
     The interval becomes the bins it OVERLAPS (the module's bin rule, not --pileup's midpoint bin): a0 = start // resolution,
     a1 = max(a0 + 1, ceil(stop / resolution)).  chrom is chr<N> or <N>, N the integer in len_vec's column 9.  ValueError for a
     malformed line, a negative coordinate and stop < start.  Host only."""
-    res = check_resolution(resolution)
-    held = set(int(c) for c in np.unique(np.asarray(len_vec)[:, 9]))
+    res, held = check_resolution(resolution), held_chroms(len_vec)
     rows, names, lines, skipped = [], [], [], 0
-    for number, line, f in annotation_lines(path):
-        if len(f) < 3 or not is_number(f[1]) or not is_number(f[2]):
-            raise ValueError("%s line %d: expected `chrom start stop [name]`, got %r" % (path, number, line))
-        start, stop, a0, a1 = _bins(path, number, f[1], f[2], res)
-        c = chrom_of(f[0])
-        if c not in held:
+    for _, _, chroms, ((start, stop),), rest in interval_lines(path, 1, "chrom start stop [name]", True):
+        c = held_chrom(chroms, held)
+        if c is None:
             skipped += 1
             continue
-        rows.append([c, a0, a1, a0, a1])
-        names.append(f[3] if len(f) > 3 else ".")
-        lines.append((f[0], start, stop, start, stop))
+        rows.append([c] + 2 * list(overlap_bins(start, stop, res)))
+        names.append(rest[0] if rest else ".")
+        lines.append((chroms[0], start, stop, start, stop))
     return _read(rows, names, lines, skipped)
 
 
@@ -211,21 +187,16 @@ def read_pairs(path, len_vec, resolution):
     """A BEDPE file `chrom1 start1 stop1 chrom2 start2 stop2 [name]` -> read_intervals' dict with the queries chrom, a0, a1,
     b0, b1: A the bins the first interval overlaps, B the second's, in the file's order.  A line whose two ends are not on one
     chromosome of len_vec is skipped and counted.  Host only."""
-    res = check_resolution(resolution)
-    held = set(int(c) for c in np.unique(np.asarray(len_vec)[:, 9]))
+    res, held = check_resolution(resolution), held_chroms(len_vec)
     rows, names, lines, skipped = [], [], [], 0
-    for number, line, f in annotation_lines(path):
-        if len(f) < 6 or not all(is_number(f[t]) for t in (1, 2, 4, 5)):
-            raise ValueError("%s line %d: expected `chrom1 start1 stop1 chrom2 start2 stop2 [name]`, got %r" % (path, number, line))
-        s1, e1, a0, a1 = _bins(path, number, f[1], f[2], res)
-        s2, e2, b0, b1 = _bins(path, number, f[4], f[5], res)
-        c = chrom_of(f[0])
-        if c not in held or chrom_of(f[3]) != c:
+    for _, _, chroms, spans, rest in interval_lines(path, 2, "chrom1 start1 stop1 chrom2 start2 stop2 [name]", True):
+        c = held_chrom(chroms, held)
+        if c is None:
             skipped += 1
             continue
-        rows.append([c, a0, a1, b0, b1])
-        names.append(f[6] if len(f) > 6 else ".")
-        lines.append((f[0], s1, e1, s2, e2))
+        rows.append([c] + [x for start, stop in spans for x in overlap_bins(start, stop, res)])
+        names.append(rest[0] if rest else ".")
+        lines.append((chroms[0], *spans[0], *spans[1]))
     return _read(rows, names, lines, skipped)
 
 
@@ -249,22 +220,14 @@ def query_lines(lines, names, counts, pairs, conf_sum=None, ctl=None):
     entropy in bits, the mean confidence (`nan` without one), with controls the controls' total and the log2 ratio of the
     dominant state, then the K counts"""
     o = np.asarray(counts)
-    K = o.shape[1]
-    sm = pile_summary(o)
-    mc = np.full(o.shape[0], np.nan) if conf_sum is None else mean_conf(conf_sum, sm["total"])
-    head = ["#chrom", "start1", "stop1", "start2", "stop2", "name", "pairs", "covered", "dominant_state", "share", "entropy_bits",
-            "mean_conf"]
-    if ctl is not None:
-        head += ["control_total", "log2_ratio"]
-        ctl_total, l2 = np.asarray(ctl).sum(axis=-1), log2_ratio(o, ctl)
-    out = ["\t".join(head + ["state_%d" % (k + 1) for k in range(K)]) + "\n"]
+    mc = np.full(o.shape[0], np.nan) if conf_sum is None else mean_conf(conf_sum, o.sum(axis=-1))
+    (core_head, tail_head), fields = summary_fields(o, ctl)
+    head = ["#chrom", "start1", "stop1", "start2", "stop2", "name", "pairs", "covered"]
+    out = ["\t".join(head + core_head + ["mean_conf"] + tail_head) + "\n"]
     for t, (chrom, s1, e1, s2, e2) in enumerate(lines):
-        dom = int(sm["dominant"][t])
-        f = [str(chrom), "%d" % s1, "%d" % e1, "%d" % s2, "%d" % e2, str(names[t]), "%d" % pairs[t], "%d" % sm["total"][t],
-             "%d" % (dom + 1), "%.6f" % sm["share"][t], "%.6f" % sm["entropy"][t], "%.6f" % mc[t]]
-        if ctl is not None:
-            f += ["%d" % ctl_total[t], "%.4f" % (l2[t, dom] if dom >= 0 else np.nan)]
-        out.append("\t".join(f + ["%d" % x for x in o[t]]) + "\n")
+        core, tail = fields((t,))
+        f = [str(chrom), "%d" % s1, "%d" % e1, "%d" % s2, "%d" % e2, str(names[t]), "%d" % pairs[t]]
+        out.append("\t".join(f + core + ["%.6f" % mc[t]] + tail) + "\n")
     return out
 
 
@@ -278,7 +241,7 @@ def query_files(path, output_path, resolution, field="state_vec", bed="", bedpe=
     res = check_resolution(resolution)
     if bool(bed) == bool(bedpe):
         raise ValueError("query_files takes a bed file or a bedpe file, one of the two")
-    shift = check_bins(res, 0, shift_bp)[1]
+    shift = check_shift(res, shift_bp)
     s, L, conf = load_map(path, field)
     read = read_intervals(bed, L, res) if bed else read_pairs(bedpe, L, res)
     q = read["queries"]

@@ -17,7 +17,7 @@ import os
 
 import numpy as np
 
-from .maps import MAX_STATES, check_len_vec, check_state_vec, device, load_map, regions, stem
+from .maps import MAX_STATES, check_K, check_len_vec, check_state_vec, device, load_map, regions, stem
 
 GRID_CAP = 1024                  # csrc/tracks.hip TRACKS_GRID_CAP: workgroups (of 256 lanes) of its kernel
 TILE_H = 32                      # csrc/tracks.hip TRACKS_TILE_H: storage rows of the tile a workgroup counts at a time ...
@@ -108,9 +108,7 @@ def state_tracks(state_vec, len_vec, windows=((0, -1),), K=None):
     s = check_state_vec(state_vec)
     L = check_len_vec(len_vec, s.shape[0])
     wins = check_windows(windows)
-    K = (int(s.max()) + 1 if s.size else 1) if K is None else int(K)
-    if K < 1 or K > MAX_STATES:
-        raise ValueError("K must be in 1 .. %d" % MAX_STATES)
+    K = check_K(s, K)
     lib, dev, stream = device()
     s_t = torch.from_numpy(s.astype(np.uint8)).to(dev)
     Q = wins.shape[0]

@@ -317,14 +317,15 @@ def test_the_entry_point_is_declared():
     m = re.search(r"PHMRF_API int phmrf_state_aggregate\((.*?)\);", re.sub(r"/\*.*?\*/", "", header, flags=re.S), re.S)
     assert m and len(m.group(1).split(",")) == 14 == len(_lib.SIGNATURES["phmrf_state_aggregate"])
     src = open(os.path.join(ROOT, "phylo_hmrf_amd", "csrc", "aggregate.hip")).read()
+    shared = open(os.path.join(ROOT, "phylo_hmrf_amd", "csrc", "interval_lists.h")).read()  # what pileup, query and aggregate compile
     for name, value in (("AGG_LANES", aggregate.LANES), ("AGG_CHUNK", aggregate.CHUNK), ("AGG_GRID_CAP", aggregate.GRID_CAP),
                         ("AGG_SMALL_AREA", aggregate.SMALL_AREA), ("AGG_WAVES", aggregate.WAVES), ("AGG_WAVE_GRID_CAP", aggregate.WAVE_GRID_CAP),
-                        ("AGG_MAX_BODY", aggregate.MAX_BODY), ("AGG_MAX_FLANK", aggregate.MAX_FLANK), ("AGG_MAX_GROUPS", aggregate.MAX_GROUPS),
-                        ("AGG_MAX_REGIONS", aggregate.MAX_REGIONS)):
+                        ("AGG_MAX_BODY", aggregate.MAX_BODY), ("AGG_MAX_FLANK", aggregate.MAX_FLANK), ("AGG_MAX_REGIONS", aggregate.MAX_REGIONS)):
         assert re.search(r"constexpr int %s = %d;" % (name, value), src), name
+    assert re.search(r"constexpr int MAX_GROUPS = %d;" % aggregate.MAX_GROUPS, shared) and '#include "interval_lists.h"' in src
     assert "constexpr int64_t AGG_MAX_TABLE = (int64_t)1 << 24;" in src and aggregate.MAX_TABLE == 1 << 24
-    assert "constexpr int AGG_COORD_LIMIT = 1 << 30;" in src and aggregate.COORD_LIMIT == 1 << 30
-    assert not re.search(r"\b(float|double)\b", re.sub(r"//.*", "", src))           # integers only
-    assert "PHMRF_DETERMINISTIC" not in src and "asm" not in re.sub(r"//.*", "", src)
+    assert "constexpr int COORD_LIMIT = 1 << 30;" in shared and aggregate.COORD_LIMIT == 1 << 30
+    assert not re.search(r"\b(float|double)\b", re.sub(r"//.*", "", src + shared))  # integers only
+    assert "PHMRF_DETERMINISTIC" not in src + shared and "asm" not in re.sub(r"//.*", "", src + shared)
     assert "aggregate.hip" in open(os.path.join(ROOT, "phylo_hmrf_amd", "csrc", "Makefile")).read()
     assert aggregate.is_small(32, 32, 2) and not aggregate.is_small(33, 32, 2) and aggregate.is_small(1, 1, 64)

@@ -199,6 +199,18 @@ def test_both_sides_of_the_threshold(gpu, wide_map):
     _check(gpu, wide_map, WIDE, features, 2, 1, 4, 1, "threshold")
 
 
+@pytest.mark.parametrize("k", (0, 1, 2, 3))
+def test_wave_rows_at_every_byte_alignment(gpu, k):
+    """a 1 x k off-diagonal region of another chromosome in front (none for k = 0) moves the slice of chromosome 1's 48 x 48
+    diagonal region to byte k of the labels; the feature [4, 44) at T = 2, F = 1 has cells of 20 x 20 = 400 bin pairs, so it
+    goes a wave per cell over rows of 20 bytes: a head, aligned words and a tail, split differently for every k"""
+    L = _len_vec(([(1, k, 0, 0, 0, 2)] if k else []) + [(48, 48, 0, 0, 1, 1)])
+    assert L[-1, 1] == k and not aggregate.is_small(40, 40, 2)
+    s = _state_vec(L, {1: _symmetric(48, 5, 61, blocky=True), 2: _symmetric(4, 5, 62)})
+    cells, votes = _check(gpu, s, L, [[1, 4, 44, 4, 44, 0, 0]], 2, 1, 5, 1, "the slice starts at byte %d" % k)
+    assert cells[0, 1:3, 1:3].sum() == 40 * 40 and votes[0, 1:3, 1:3].sum() == 4
+
+
 # ---- 4: ties ------------------------------------------------------------------------------------------------------------------
 def test_ties_go_to_the_lowest_state(gpu):
     i, j = np.indices((40, 40))

@@ -312,6 +312,8 @@ def test_constants_are_the_headers_and_the_sources():
     assert "PILEUP_CHUNK = %d;" % pileup.CHUNK in src
     assert "PILEUP_GRID_CAP = %d;" % pileup.GRID_CAP in src
     assert "PILEUP_MAX_FLANK = %d;" % pileup.MAX_FLANK in src
-    assert "PILEUP_MAX_GROUPS = %d;" % pileup.MAX_GROUPS in src
-    assert '#include "runs.h"' in src and "getenv" not in src
-    assert "pileup.hip" in open(os.path.join(ROOT, "phylo_hmrf_amd", "csrc", "Makefile")).read()
+    shared = open(os.path.join(ROOT, "phylo_hmrf_amd", "csrc", "interval_lists.h")).read()  # what pileup, query and aggregate compile
+    assert "constexpr int MAX_GROUPS = %d;" % pileup.MAX_GROUPS in shared
+    assert '#include "interval_lists.h"' in src and '#include "runs.h"' in shared and "getenv" not in src + shared
+    mk = open(os.path.join(ROOT, "phylo_hmrf_amd", "csrc", "Makefile")).read()
+    assert "pileup.hip" in mk and "interval_lists.h" in mk

@@ -273,4 +273,6 @@ def test_the_entry_point_is_declared():
     for name, value in (("RECT_TILE_H", query.TILE_H), ("RECT_TILE_W", query.TILE_W), ("RECT_VEC_MIN", query.VEC_MIN),
                         ("RECT_WAVES", query.WAVES), ("RECT_GRID_CAP", query.GRID_CAP)):
         assert re.search(r"constexpr int %s = %d;" % (name, value), src), name
+    shared = open(os.path.join(ROOT, "phylo_hmrf_amd", "csrc", "interval_lists.h")).read()  # what pileup, query and aggregate compile
+    assert "constexpr int COORD_LIMIT = 1 << 30;" in shared and query.COORD_LIMIT == 1 << 30 and '#include "interval_lists.h"' in src
     assert "query.hip" in open(os.path.join(ROOT, "phylo_hmrf_amd", "csrc", "Makefile")).read()

@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """Time the rescaled pile-up of a state map (phmrf_state_aggregate) on tools/enrich_time.py's genome map (default cfg3: whole
-genome at 50 kb, 26 blocks, 88.8 M nodes, K = 20) at a body of --body (32) and a flank of --flank (16) cells with two lists:
+genome at 50 kb, 26 blocks, 88.8 M nodes, K = 20) at a body of --body (32) and a flank of --flank (16) cells with three lists:
 
     tads     consecutive intervals of 10 .. 40 bins that tile every chromosome (about 3,000): one group
     domains  consecutive intervals of 100 .. 500 bins that tile every chromosome (about 200) with their controls --shift (100)
              bins along the diagonal to either side (with_controls): two groups
+    large    consecutive intervals of 600 .. 2,000 bins that tile every chromosome (about 100): one group.  At a body of 32
+             ceil(600 / 32)^2 = 361 > SMALL_AREA, so every one of them goes a wave per pile cell (aggregate_wave_kernel); the
+             other two lists stay with the lane kernel
 
 The map and every chromosome's features are on the GPU before anything is timed.  Per list, summed over the chromosomes, in
 milliseconds by HIP events around the library call (each call allocates and zeroes its tables, uploads its regions, runs its
@@ -196,6 +199,8 @@ def main():
                nodes=int(sv.size), blocks=int(lv.shape[0]), K=K, inputs={})
     out["inputs"]["tads"] = run("tads", m_t, sv, lv, K, tads, 1)
     out["inputs"]["domains"] = dict(run("domains", m_t, sv, lv, K, domains, 2), shift=a.shift)
+    large = tiling(bins, 600, 2000, rng)
+    out["inputs"]["large"] = run("large", m_t, sv, lv, K, large, 1)
     out["not_measured"] = NOT_MEASURED
     print(json.dumps(out))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
