@@ -706,6 +706,41 @@ PHMRF_API int phmrf_state_aggregate(const uint8_t* labels_dev, int64_t n_labels,
                                     const uint8_t* flip_dev_or_null /* NULL: all 0 */, int64_t* cells_host /* [G][P][P][K] */,
                                     int64_t* votes_host /* [G][P][P][K] */, void* hip_stream);
 
+/* phmrf_regrid_states: ONE CHROMOSOME's state map resampled onto ONE region of a grid of another resolution and another
+ * region layout (no block, no ABI bump).  labels_dev and regions_host are phmrf_state_aggregate's: the
+ * whole state_vec and the R source regions (lo, H, W, start_bin1, start_bin2, diagonal) of the chromosome.  A source bin has a
+ * units and a target bin b units (the two bin sizes divided by their greatest common divisor): source bin p covers the units
+ * [p a, (p + 1) a), target bin x the units [x b, (x + 1) b), and ov(x, p) = max(0, min((x + 1) b, (p + 1) a) - max(x b, p a)).
+ * The target region is H x W target bins from (start_bin1, start_bin2) on, its n_t stored nodes in the node order of
+ * phmrf_smooth_labels (a diagonal target stores x <= y only).  For its cell (x, y), over the stored nodes (p, q) of all R
+ * regions in state k,
+ *   votes[k] = sum of ov(x, p) ov(y, q) + [p != q] ov(x, q) ov(y, p)
+ * -- the symmetric chromosome matrix read through all its regions; a target cell on the diagonal counts off-diagonal source
+ * cells twice, as phmrf_render_states does.  covered = sum_k votes (<= b^2), support = max_k votes, the cell's state is the
+ * lowest k at the maximum when covered >= min_cover and `fill` otherwise.
+ *   state_dev            device u8 [n_t]
+ *   support_dev_or_null  device u32 [n_t]: support, of called and uncalled cells alike
+ *   covered_dev_or_null  device u32 [n_t]: covered
+ *   hist_host            host int64 [K + 1]: hist[k] = the stored target cells called k, hist[K] the uncalled ones
+ *   mixed_host           host int64: the called cells with support < covered
+ * The source regions must not overlap on the full matrix, directly or through their mirror images (an off-diagonal region whose
+ * row and column ranges share a bin overlaps its own; a diagonal region has start_bin1 == start_bin2): covered / b^2 is a
+ * true share.  A source node that no stored target cell of the call reads is never inspected: a label >= K there is no error.
+ * Queued on hip_stream, returns when done.  Integers only: the same bytes from run to run, whatever PHMRF_DETERMINISTIC says.
+ * PHMRF_ERR_INVALID (nothing written, on the host or the device) for a NULL labels_dev, regions_host, state_dev, hist_host or
+ * mixed_host, n_labels < 1, R < 1, K < 1, a < 1, b < 1, min_cover outside 1 .. b^2, fill outside 0 .. 255, a target with H < 1,
+ * W < 1, a diagonal flag that is not 0 or 1, a non-square diagonal block, a negative start bin or a diagonal target with
+ * unequal start bins, a source region that phmrf_state_aggregate refuses as invalid or that is diagonal with unequal start
+ * bins, overlapping source regions (the message names them), or a label >= K inside a read cell;
+ * PHMRF_ERR_UNSUPPORTED (nothing written) for K > 64, R > 64, a or b > 2^15, a start bin >= 2^30 or n >= 2^31 - 64 of the
+ * target or of a source region. */
+PHMRF_API int phmrf_regrid_states(const uint8_t* labels_dev, int64_t n_labels, int R,
+                                  const int64_t* regions_host /* [R][6]: lo, H, W, start_bin1, start_bin2, diagonal */,
+                                  int K, int a, int b, int H, int W, int diagonal, int64_t start_bin1, int64_t start_bin2,
+                                  int64_t min_cover, int fill, uint8_t* state_dev /* [n_t] */,
+                                  uint32_t* support_dev_or_null /* [n_t] */, uint32_t* covered_dev_or_null /* [n_t] */,
+                                  int64_t* hist_host /* [K+1] */, int64_t* mixed_host, void* hip_stream);
+
 /* ---- profiling the states ------------------------------------------------------------------------- */
 /* What a state IS, from the block's resident f32 observations x (the uploaded float64 rounded to nearest) and its current
  * labels (no ABI bump: the calls only add entry points).  Both calls run over the nodes the block OWNS

@@ -218,6 +218,17 @@ def parse_args(argv=None):
                       "this many bp")
     parser.add_option("--aggregate_colors", default="", help="--aggregate: a text file of R G B rows (0 .. 255), one per state, in "
                       "place of the built-in palette")
+    parser.add_option("--regrid", default="", help="skip loading data and fitting: resample the states of this .mat, whose bins "
+                      "are --regrid_from bp, onto bins of --resolution bp (every target bin pair takes the state that covers most "
+                      "of it, the lowest on ties, by exact overlap areas over the chromosome's full matrix); writes "
+                      "regrid_<stem>_<resolution>.mat (a state map every other mode reads, with conf = the vote share) and "
+                      "regrid_<stem>_<resolution>.txt under --output")
+    parser.add_option("--regrid_from", default="", help="--regrid: the bin size of the .mat in bp (required)")
+    parser.add_option("--regrid_like", default="", help="--regrid: a .mat at --resolution whose len_vec gives the target regions "
+                      "(copied as it is, so that --compare accepts the two files); default: the source's own regions on the new bins")
+    parser.add_option("--regrid_field", default="state_vec", help="--regrid: state_vec or state_vec_smooth")
+    parser.add_option("--regrid_cover", default="50", help="--regrid: a target bin pair is called when the source covers at least "
+                      "this many percent of it, 0 .. 100 (0: any coverage); else it takes the state K, `uncovered`")
     parser.add_option("-h", "--help", action="help")
     opts, _ = parser.parse_args(argv)
     return opts
@@ -332,7 +343,7 @@ def segment_settings(m, num_states, resolution, num_neighbor, filter_mode, filte
     return (out["num_states"], out["resolution"], out["num_neighbor"], out["filter_mode"], out["filter_sigma"], out["dtype"])
 
 
-def check_ancestral(ancestral, segment, postprocess):
+def check_ancestral(ancestral, segment, postprocess, regrid=""):
     """--ancestral posterior|called reconstructs on a segmentation's labels: only together with --segment"""
     if not ancestral:
         return
@@ -340,19 +351,21 @@ def check_ancestral(ancestral, segment, postprocess):
         raise SystemExit("--ancestral must be posterior or called, not %r (it goes with --segment)" % (ancestral,))
     if postprocess:
         raise SystemExit("--ancestral cannot be combined with --postprocess, which loads no data: it goes with --segment")
+    if regrid:
+        raise SystemExit("--ancestral cannot be combined with --regrid, which loads no data: it goes with --segment")
     if not segment:
         raise SystemExit("--ancestral needs --segment: the ancestors are reconstructed with a saved model on the labels of "
                          "its segmentation")
 
 
-def check_profile(profile, profile_quantiles, postprocess, compare, consensus="", query="", aggregate=""):
+def check_profile(profile, profile_quantiles, postprocess, compare, consensus="", query="", aggregate="", regrid=""):
     """--profile 1 needs the observations on the GPU: it goes with a fit or --segment -> the quantiles, or None when off"""
     if str(profile) not in ("0", "1"):
         raise SystemExit("--profile must be 0 or 1")
     if str(profile) == "0":
         return None
     for name, value in (("--postprocess", postprocess), ("--compare", compare), ("--consensus", consensus), ("--query", query),
-                        ("--aggregate", aggregate)):
+                        ("--aggregate", aggregate), ("--regrid", regrid)):
         if value:
             raise SystemExit("--profile 1 cannot be combined with %s, which loads no data: the profile needs the observations"
                              % name)
@@ -376,7 +389,7 @@ def write_profile(model, state_vec, quantiles, output_path, run_id, K, species, 
 
 
 def check_compare(compare, compare_with, compare_field, compare_match, segment, postprocess, ancestral, save_model,
-                  filter_device, consensus="", query="", aggregate=""):
+                  filter_device, consensus="", query="", aggregate="", regrid=""):
     """--compare A.mat --compare_with B.mat reads two finished state maps: it goes with nothing that loads data or fits"""
     if not compare and not compare_with:
         return
@@ -385,7 +398,7 @@ def check_compare(compare, compare_with, compare_field, compare_match, segment, 
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--ancestral", ancestral),
                         ("--save_model", save_model), ("--filter_device 1", str(filter_device) == "1"),
                         ("--consensus", consensus), ("--query", query),
-                        ("--aggregate", aggregate)):
+                        ("--aggregate", aggregate), ("--regrid", regrid)):
         if value:
             raise SystemExit("--compare cannot be combined with %s: it loads no data and fits nothing" % name)
     if compare_field not in ("state_vec", "state_vec_smooth"):
@@ -395,14 +408,14 @@ def check_compare(compare, compare_with, compare_field, compare_match, segment, 
 
 
 def check_domains(domains, domains_field, segment, postprocess, compare, ancestral, save_model, profile, filter_device,
-                  consensus="", query="", aggregate=""):
+                  consensus="", query="", aggregate="", regrid=""):
     """--domains FILE.mat reads one finished state map: it goes with nothing that loads data or fits"""
     if not domains:
         return
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare),
                         ("--ancestral", ancestral), ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
                         ("--filter_device 1", str(filter_device) == "1"), ("--consensus", consensus), ("--query", query),
-                        ("--aggregate", aggregate)):
+                        ("--aggregate", aggregate), ("--regrid", regrid)):
         if value:
             raise SystemExit("--domains cannot be combined with %s: it loads no data and fits nothing" % name)
     if domains_field not in ("state_vec", "state_vec_smooth"):
@@ -410,14 +423,14 @@ def check_domains(domains, domains_field, segment, postprocess, compare, ancestr
 
 
 def check_render(render, render_field, render_side, render_outline, render_conf, segment, postprocess, compare, domains,
-                 ancestral, save_model, profile, filter_device, consensus="", query="", aggregate=""):
+                 ancestral, save_model, profile, filter_device, consensus="", query="", aggregate="", regrid=""):
     """--render FILE.mat reads one finished state map: it goes with nothing that loads data or fits -> the side, or None"""
     if not render:
         return None
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
                         ("--ancestral", ancestral), ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
                         ("--filter_device 1", str(filter_device) == "1"), ("--consensus", consensus), ("--query", query),
-                        ("--aggregate", aggregate)):
+                        ("--aggregate", aggregate), ("--regrid", regrid)):
         if value:
             raise SystemExit("--render cannot be combined with %s: it loads no data and fits nothing" % name)
     if render_field not in ("state_vec", "state_vec_smooth"):
@@ -435,7 +448,7 @@ def check_render(render, render_field, render_side, render_outline, render_conf,
 
 
 def check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment, postprocess, compare, domains, ancestral,
-                 save_model, profile, filter_device, consensus="", query="", aggregate=""):
+                 save_model, profile, filter_device, consensus="", query="", aggregate="", regrid=""):
     """--tracks FILE.mat reads one finished state map: it goes with nothing that loads data or fits -> the windows in bins,
     or None"""
     if not tracks:
@@ -444,7 +457,7 @@ def check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment,
                         ("--domains", domains), ("--ancestral", ancestral), ("--save_model", save_model),
                         ("--profile 1", str(profile) == "1"), ("--filter_device 1", str(filter_device) == "1"),
                         ("--consensus", consensus), ("--query", query),
-                        ("--aggregate", aggregate)):
+                        ("--aggregate", aggregate), ("--regrid", regrid)):
         if value:
             raise SystemExit("--tracks cannot be combined with %s: it loads no data and fits nothing" % name)
     if tracks_field not in ("state_vec", "state_vec_smooth"):
@@ -457,7 +470,7 @@ def check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment,
 
 
 def check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments, resolution, segment, postprocess, compare,
-                 domains, render, tracks, ancestral, save_model, profile, filter_device, consensus="", query="", aggregate=""):
+                 domains, render, tracks, ancestral, save_model, profile, filter_device, consensus="", query="", aggregate="", regrid=""):
     """--enrich FILE.mat --enrich_bed FILE reads one finished state map and an annotation: it goes with nothing that loads data
     or fits, and with no other reader of a state map -> the window (d_min, d_max) in bins, or None"""
     if not enrich:
@@ -470,7 +483,7 @@ def check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments,
                         ("--render", render), ("--tracks", tracks), ("--ancestral", ancestral), ("--save_model", save_model),
                         ("--profile 1", str(profile) == "1"), ("--filter_device 1", str(filter_device) == "1"),
                         ("--consensus", consensus), ("--query", query),
-                        ("--aggregate", aggregate)):
+                        ("--aggregate", aggregate), ("--regrid", regrid)):
         if value:
             raise SystemExit("--enrich cannot be combined with %s: it loads no data and fits nothing" % name)
     if enrich_field not in ("state_vec", "state_vec_smooth"):
@@ -508,7 +521,8 @@ def check_enrich_null(enrich, enrich_null="0", enrich_null_min="1000000", enrich
 
 
 def check_pileup(pileup, pileup_bed, pileup_bedpe, pileup_field, pileup_flank, pileup_shift, resolution, segment, postprocess,
-                 compare, domains, render, tracks, enrich, ancestral, save_model, profile, filter_device, consensus="", query="", aggregate=""):
+                 compare, domains, render, tracks, enrich, ancestral, save_model, profile, filter_device, consensus="", query="", aggregate="",
+                 regrid=""):
     """--pileup FILE.mat with --pileup_bed FILE or --pileup_bedpe FILE reads one finished state map and a list of anchors: it
     goes with nothing that loads data or fits, and with no other reader of a state map -> (the flank, the shift) in bins, or
     None"""
@@ -522,7 +536,7 @@ def check_pileup(pileup, pileup_bed, pileup_bedpe, pileup_field, pileup_flank, p
                         ("--render", render), ("--tracks", tracks), ("--enrich", enrich), ("--ancestral", ancestral),
                         ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
                         ("--filter_device 1", str(filter_device) == "1"), ("--consensus", consensus), ("--query", query),
-                        ("--aggregate", aggregate)):
+                        ("--aggregate", aggregate), ("--regrid", regrid)):
         if value:
             raise SystemExit("--pileup cannot be combined with %s: it loads no data and fits nothing" % name)
     if pileup_field not in ("state_vec", "state_vec_smooth"):
@@ -535,7 +549,8 @@ def check_pileup(pileup, pileup_bed, pileup_bedpe, pileup_field, pileup_flank, p
 
 
 def check_consensus(consensus, consensus_field, consensus_match, consensus_support, consensus_area, segment, postprocess,
-                    compare, domains, render, tracks, enrich, pileup, ancestral, save_model, profile, filter_device, query="", aggregate=""):
+                    compare, domains, render, tracks, enrich, pileup, ancestral, save_model, profile, filter_device, query="", aggregate="",
+                    regrid=""):
     """--consensus A.mat,B.mat,... reads finished state maps of the same regions: it goes with nothing that loads data or
     fits, and with no other reader of a state map -> (the files, min_support or None, min_area or None), or None"""
     if not consensus:
@@ -544,7 +559,7 @@ def check_consensus(consensus, consensus_field, consensus_match, consensus_suppo
                         ("--render", render), ("--tracks", tracks), ("--enrich", enrich), ("--pileup", pileup),
                         ("--ancestral", ancestral), ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
                         ("--filter_device 1", str(filter_device) == "1"), ("--query", query),
-                        ("--aggregate", aggregate)):
+                        ("--aggregate", aggregate), ("--regrid", regrid)):
         if value:
             raise SystemExit("--consensus cannot be combined with %s: it loads no data and fits nothing" % name)
     from phylo_hmrf_amd.consensus import CONSENSUS_MAPS
@@ -568,7 +583,7 @@ def check_consensus(consensus, consensus_field, consensus_match, consensus_suppo
 
 
 def check_query(query, query_bed, query_bedpe, query_field, query_shift, resolution, segment, postprocess, compare, domains,
-                render, tracks, enrich, pileup, consensus, ancestral, save_model, profile, filter_device, aggregate=""):
+                render, tracks, enrich, pileup, consensus, ancestral, save_model, profile, filter_device, aggregate="", regrid=""):
     """--query FILE.mat with --query_bed FILE or --query_bedpe FILE reads one finished state map and a list of intervals: it
     goes with nothing that loads data or fits, and with no other reader of a state map -> the shift in bins, or None"""
     if not query:
@@ -581,7 +596,7 @@ def check_query(query, query_bed, query_bedpe, query_field, query_shift, resolut
                         ("--render", render), ("--tracks", tracks), ("--enrich", enrich), ("--pileup", pileup),
                         ("--consensus", consensus), ("--ancestral", ancestral), ("--save_model", save_model),
                         ("--profile 1", str(profile) == "1"), ("--filter_device 1", str(filter_device) == "1"),
-                        ("--aggregate", aggregate)):
+                        ("--aggregate", aggregate), ("--regrid", regrid)):
         if value:
             raise SystemExit("--query cannot be combined with %s: it loads no data and fits nothing" % name)
     if query_field not in ("state_vec", "state_vec_smooth"):
@@ -595,7 +610,7 @@ def check_query(query, query_bed, query_bedpe, query_field, query_shift, resolut
 
 def check_aggregate(aggregate, aggregate_bed, aggregate_bedpe, aggregate_field, aggregate_body, aggregate_flank, aggregate_shift,
                     aggregate_min, aggregate_colors, resolution, segment, postprocess, compare, domains, render, tracks, enrich,
-                    pileup, consensus, query, ancestral, save_model, profile, filter_device):
+                    pileup, consensus, query, ancestral, save_model, profile, filter_device, regrid=""):
     """--aggregate FILE.mat with --aggregate_bed FILE or --aggregate_bedpe FILE reads one finished state map and a list of
     features: it goes with nothing that loads data or fits, and with no other reader of a state map -> (the body, the flank
     in cells, the shift in bins, the shortest feature in bp), or None"""
@@ -612,7 +627,8 @@ def check_aggregate(aggregate, aggregate_bed, aggregate_bedpe, aggregate_field, 
     for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
                         ("--render", render), ("--tracks", tracks), ("--enrich", enrich), ("--pileup", pileup),
                         ("--consensus", consensus), ("--query", query), ("--ancestral", ancestral), ("--save_model", save_model),
-                        ("--profile 1", str(profile) == "1"), ("--filter_device 1", str(filter_device) == "1")):
+                        ("--profile 1", str(profile) == "1"), ("--filter_device 1", str(filter_device) == "1"),
+                        ("--regrid", regrid)):
         if value:
             raise SystemExit("--aggregate cannot be combined with %s: it loads no data and fits nothing" % name)
     if aggregate_field not in ("state_vec", "state_vec_smooth"):
@@ -635,6 +651,42 @@ def check_aggregate(aggregate, aggregate_bed, aggregate_bedpe, aggregate_field, 
         raise SystemExit("--aggregate with --aggregate_shift %s: %s" % (aggregate_shift, e))
 
 
+def check_regrid(regrid, regrid_from, regrid_like, regrid_field, regrid_cover, resolution, segment, postprocess, compare, domains,
+                 render, tracks, enrich, pileup, consensus, query, aggregate, ancestral, save_model, profile, filter_device):
+    """--regrid SRC.mat --regrid_from BP reads one finished state map and writes it on bins of --resolution bp: it goes with
+    nothing that loads data or fits, and with no other reader of a state map -> (the source's bin size in bp, the cover in
+    percent), or None.  Without --regrid a sub-option is told from its absence by its default text alone, as --aggregate's are:
+    `--regrid_cover 50` and `--regrid_field state_vec` pass for no option, `--regrid_cover 50.0` is refused."""
+    if not regrid:
+        if (regrid_from, regrid_like, regrid_field, str(regrid_cover)) != ("", "", "state_vec", "50"):
+            raise SystemExit("--regrid_from, --regrid_like, --regrid_field and --regrid_cover go with --regrid")
+        return None
+    if not regrid_from:
+        raise SystemExit("--regrid needs --regrid_from: the bin size of the .mat in bp (--resolution is the target's)")
+    for name, value in (("--segment", segment), ("--postprocess", postprocess), ("--compare", compare), ("--domains", domains),
+                        ("--render", render), ("--tracks", tracks), ("--enrich", enrich), ("--pileup", pileup),
+                        ("--consensus", consensus), ("--query", query), ("--aggregate", aggregate), ("--ancestral", ancestral),
+                        ("--save_model", save_model), ("--profile 1", str(profile) == "1"),
+                        ("--filter_device 1", str(filter_device) == "1")):
+        if value:
+            raise SystemExit("--regrid cannot be combined with %s: it loads no data and fits nothing" % name)
+    if regrid_field not in ("state_vec", "state_vec_smooth"):
+        raise SystemExit("--regrid_field must be state_vec or state_vec_smooth, not %r" % (regrid_field,))
+    from fractions import Fraction
+    from phylo_hmrf_amd.regrid import ratio
+    try:
+        src, cover = int(regrid_from), Fraction(str(regrid_cover))
+    except (ValueError, ZeroDivisionError):
+        raise SystemExit("--regrid_from must be an integer and --regrid_cover a number")
+    if not 0 <= cover <= 100:
+        raise SystemExit("--regrid_cover must lie in 0 .. 100 percent, not %s" % regrid_cover)
+    try:
+        ratio(src, int(resolution))
+    except ValueError as e:
+        raise SystemExit("--regrid with --regrid_from %s and --resolution %s: %s" % (regrid_from, resolution, e))
+    return src, str(regrid_cover)
+
+
 def run(num_states, chromvec, root_path, multiple, species_name, sort_states, run_id1, cons_param, method_mode,
         initial_mode, initial_weight, initial_weight1, initial_magnitude, position1, position2, filter_sigma, beta,
         beta1, num_neighbor, filter_mode, conv_threshold, estimate_type, simu_version, annotation, reload_mode,
@@ -651,40 +703,52 @@ def run(num_states, chromvec, root_path, multiple, species_name, sort_states, ru
         consensus_area="-1", query="", query_bed="", query_bedpe="", query_field="state_vec", query_shift="0",
         enrich_null="0", enrich_null_min="1000000", enrich_null_seed="0", aggregate="", aggregate_bed="", aggregate_bedpe="",
         aggregate_field="state_vec", aggregate_body="32", aggregate_flank="16", aggregate_shift="0", aggregate_min="0",
-        aggregate_colors=""):
+        aggregate_colors="", regrid="", regrid_from="", regrid_like="", regrid_field="state_vec", regrid_cover="50"):
+    resample = check_regrid(regrid, regrid_from, regrid_like, regrid_field, regrid_cover, resolution, segment, postprocess,
+                            compare or compare_with, domains, render, tracks, enrich, pileup, consensus, query, aggregate,
+                            ancestral, save_model, profile, filter_device)
     grid = check_aggregate(aggregate, aggregate_bed, aggregate_bedpe, aggregate_field, aggregate_body, aggregate_flank,
                            aggregate_shift, aggregate_min, aggregate_colors, resolution, segment, postprocess,
                            compare or compare_with, domains, render, tracks, enrich, pileup, consensus, query, ancestral,
-                           save_model, profile, filter_device)
+                           save_model, profile, filter_device, regrid=regrid)
     check_query(query, query_bed, query_bedpe, query_field, query_shift, resolution, segment, postprocess,
                 compare or compare_with, domains, render, tracks, enrich, pileup, consensus, ancestral, save_model, profile,
-                filter_device, aggregate=aggregate)
+                filter_device, aggregate=aggregate, regrid=regrid)
     vote = check_consensus(consensus, consensus_field, consensus_match, consensus_support, consensus_area, segment, postprocess,
                            compare or compare_with, domains, render, tracks, enrich, pileup, ancestral, save_model, profile,
-                           filter_device, query=query, aggregate=aggregate)
+                           filter_device, query=query, aggregate=aggregate, regrid=regrid)
     check_pileup(pileup, pileup_bed, pileup_bedpe, pileup_field, pileup_flank, pileup_shift, resolution, segment, postprocess,
                  compare or compare_with, domains, render, tracks, enrich, ancestral, save_model, profile, filter_device,
-                 consensus=consensus, query=query, aggregate=aggregate)
+                 consensus=consensus, query=query, aggregate=aggregate, regrid=regrid)
     check_enrich(enrich, enrich_bed, enrich_field, enrich_dist, enrich_segments, resolution, segment, postprocess,
                  compare or compare_with, domains, render, tracks, ancestral, save_model, profile, filter_device,
-                 consensus=consensus, query=query, aggregate=aggregate)
+                 consensus=consensus, query=query, aggregate=aggregate, regrid=regrid)
     null = check_enrich_null(enrich, enrich_null, enrich_null_min, enrich_null_seed, resolution)
     check_tracks(tracks, tracks_field, tracks_dist, resolution, render, segment, postprocess, compare or compare_with, domains,
-                 ancestral, save_model, profile, filter_device, consensus=consensus, query=query, aggregate=aggregate)
+                 ancestral, save_model, profile, filter_device, consensus=consensus, query=query, aggregate=aggregate,
+                 regrid=regrid)
     side = check_render(render, render_field, render_side, render_outline, render_conf, segment, postprocess,
-                        compare or compare_with, domains, ancestral, save_model, profile, filter_device, consensus=consensus, query=query, aggregate=aggregate)
+                        compare or compare_with, domains, ancestral, save_model, profile, filter_device, consensus=consensus, query=query,
+                        aggregate=aggregate, regrid=regrid)
     check_domains(domains, domains_field, segment, postprocess, compare or compare_with, ancestral, save_model, profile,
-                  filter_device, consensus=consensus, query=query, aggregate=aggregate)
-    profile_q = check_profile(profile, profile_quantiles, postprocess, compare, consensus=consensus, query=query, aggregate=aggregate)
+                  filter_device, consensus=consensus, query=query, aggregate=aggregate, regrid=regrid)
+    profile_q = check_profile(profile, profile_quantiles, postprocess, compare, consensus=consensus, query=query, aggregate=aggregate,
+                              regrid=regrid)
     check_compare(compare, compare_with, compare_field, compare_match, segment, postprocess, ancestral, save_model,
-                  filter_device, consensus=consensus, query=query, aggregate=aggregate)
-    check_ancestral(ancestral, segment, postprocess)
+                  filter_device, consensus=consensus, query=query, aggregate=aggregate, regrid=regrid)
+    check_ancestral(ancestral, segment, postprocess, regrid=regrid)
     filter_device = int(filter_device)
     if filter_device not in (0, 1):
         raise SystemExit("--filter_device must be 0 or 1")
     if filter_device and (int(reload_mode) == 1 or int(synthetic) > 0 or postprocess):
         raise SystemExit("--filter_device 1 runs the raw loader's filter on the GPU: it cannot be combined with --reload 1, "
                          "--synthetic or --postprocess, where nothing is filtered")
+    if resample:
+        from phylo_hmrf_amd.regrid import regrid_files
+        out = regrid_files(regrid, str(output_path), resample[0], int(resolution), like=regrid_like, field=regrid_field,
+                           cover=resample[1])
+        print("regridded map written: %s" % out)
+        return out
     if vote:
         from phylo_hmrf_amd.consensus import consensus_files
         files, support, area = vote
@@ -940,4 +1004,5 @@ if __name__ == "__main__":
         enrich_null_seed=opts.enrich_null_seed, aggregate=opts.aggregate, aggregate_bed=opts.aggregate_bed,
         aggregate_bedpe=opts.aggregate_bedpe, aggregate_field=opts.aggregate_field, aggregate_body=opts.aggregate_body,
         aggregate_flank=opts.aggregate_flank, aggregate_shift=opts.aggregate_shift, aggregate_min=opts.aggregate_min,
-        aggregate_colors=opts.aggregate_colors)
+        aggregate_colors=opts.aggregate_colors, regrid=opts.regrid, regrid_from=opts.regrid_from, regrid_like=opts.regrid_like,
+        regrid_field=opts.regrid_field, regrid_cover=opts.regrid_cover)

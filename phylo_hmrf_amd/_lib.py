@@ -130,6 +130,7 @@ SIGNATURES = {
     "phmrf_state_pileup": [_vp, _i, _i, _i, _i, _i, _i, _lp, _vp, _vp, _vp, _lp, _vp],
     "phmrf_rect_states": [_vp, _vp, _i, _i, _i, _i, _i64, _ip, _ip, ctypes.POINTER(ctypes.c_uint8), _i64, _lp, _lp, _vp],
     "phmrf_state_aggregate": [_vp, _i64, _i, _lp, _i, _i, _i, _i, _lp, _vp, _vp, _lp, _lp, _vp],
+    "phmrf_regrid_states": [_vp, _i64, _i, _lp, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _i, _vp, _vp, _vp, _lp, _lp, _vp],
     "phmrf_state_hist": [_vp, _i, _i, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)],
     "phmrf_state_moments": [_vp, _i64, _lp, _dp, _dp, _lp],
     "phmrf_filter_diffusion": [_vp, _vp, _i64, _i64, _i, _d, _d, _i, _vp],

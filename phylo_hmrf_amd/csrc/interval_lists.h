@@ -1,7 +1,8 @@
 // What the kernels that count a state map under a LIST of intervals share (pileup.hip, query.hip, aggregate.hip; DESIGN.md
-// section 7): the limit of a coordinate, the clip of a rectangle to a region, the table of the groups' entries and chunks
-// (pileup, aggregate; each kernel decomposes its items itself), a lane's private LDS column of 16-bit counters (pileup,
-// aggregate) and, on the host, the zeroed output table with the flag word behind it (all three).  Integers only.
+// section 7; regrid.hip takes the first, the second and the last): the limit of a coordinate, the clip of a rectangle to a
+// region, the table of the groups' entries and chunks (pileup, aggregate; each kernel decomposes its items itself), a lane's
+// private LDS column of 16-bit counters (pileup, aggregate) and, on the host, the zeroed output table with the flag word
+// behind it (all three, and regrid).  Integers only.
 #pragma once
 
 #include "runs.h"

@@ -1,8 +1,8 @@
 // What the post-processing's kernel files share (smooth.hip, compare.hip, consensus.hip, profile.hip, domains.hip, tracks.hip,
-// enrich.hip, enrich_null.hip, pileup.hip, query.hip, aggregate.hip): the capped grid, the wave helpers of their integer
+// enrich.hip, enrich_null.hip, pileup.hip, query.hip, aggregate.hip, regrid.hip): the capped grid, the wave helpers of their integer
 // accumulations -- one atomic per RUN of equal destination among consecutive lanes, because state maps are piecewise constant
-// --, the split of a label row into aligned words (tracks, enrich, enrich_null, query, aggregate), the order of a wave's LDS
-// traffic (query, aggregate) and the tiles of a distance window (tracks; enrich and enrich_null through enrich_tiles.h), the
+// --, the split of a label row into aligned words (tracks, enrich, enrich_null, query, aggregate, regrid), the order of a wave's LDS
+// traffic (query, aggregate, regrid) and the tiles of a distance window (tracks; enrich and enrich_null through enrich_tiles.h), the
 // full-matrix area of a grid component, and on the host the owner of a call's device buffers and the
 // checks of a region's and a window's arguments (preprocess.hip and render.hip take those too).  What only the interval-list
 // kernels share (pileup, query, aggregate) is in interval_lists.h.
